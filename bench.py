@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- frames/s of the FastDepth MobileNetSkipAdd hot path on MI355X (BASELINE.json `metric`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]            (N > 1: re-launches itself under torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]    (N > 1: re-launches itself under torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
@@ -11,10 +11,15 @@ runs its own batch of 32 (weak scaling; inference shards over frames with no col
 the timed region is bracketed by barrier + torch.cuda.synchronize() and the max over ranks is taken.  Setup (plan creation,
 weight packing and 0.3 s of untimed forwards that take a freshly leased GPU past its power-management transient: `config.untimed_device_wakeup_steps_before_warmup`)
 precedes the W warm-up steps; exactly K full steps are timed.
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
-  windows_ms_per_step, host_enqueue_ms_per_step
-                    six consecutive windows of K steps (the first IS the headline) and the host's enqueue time per step of the headline window:
-                    shows whether a run sat on a clock transient (a later window faster), on the host, or on neither
+  --dump-outputs DIR  after the timed steps, rank 0 writes the depth map its last timed step returned (batch x 1 x 224 x 224, float32,
+                    6.4 MB at batch 32) as DIR/depth.npy; weights and inputs are seeded, so equal arguments give equal inputs run to run
+Rank 0 prints ONE JSON line.  A plain run measures the headline and nothing else; besides the contract fields the line carries
+  host_enqueue_ms_per_step
+                    the host's enqueue time per step of the headline window: close to ms_per_step when the run sat on the host
+With --full it also carries the figures below, each measured in runs of its own after the headline (minutes in all):
+  windows_ms_per_step
+                    six consecutive windows of K steps (the first IS the headline): shows whether a run sat on a clock transient
+                    (a later window faster)
   roofline          the kernel symbol with the largest share of device time, timed live with HIP events on the launch stream,
                     priced against the fp32 MFMA peak or HBM bandwidth (MI355X_MICROARCH.md); `traffic` from the committed PMC summary
   whole_step        algorithmic bytes / flops of the step and its layer-wise roofline bound sum_l max(bytes/HBM, flops/MFMA)
@@ -23,8 +28,8 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
                     configs[3] at N = 8), each with its own `roofline` (dominant kernel family, fd_trace) and, for N > 1, the all-reduce time
                     and how much of it backward hides
   other_configs     configs[4] (pruned fp16 B=64), 16-bit storage B=32, B=1 latency -- N = 1 only, each with a `roofline`
-  cpu_baseline      N = 1, rank 0: the reference's UNMODIFIED module (kind "reference") when /root/reference exists, otherwise the
-                    oracle's torch-functional restatement (kind "port": the same ATen CPU kernels), on the host cores: inference at
+  cpu_baseline      N = 1, rank 0: the TorchScript traces of the reference's unmodified module that build() makes (kind "reference")
+                    when they are present, otherwise the oracle's torch-functional restatement (kind "port": the same ATen CPU kernels), on the host cores: inference at
                     B in {1, 8, 32} and the train step (L1Loss + SGD) at B in {8, 32}; warm-up + repeated timed runs, median
                     (protocol of the reference's deploy/tx2_run_tvm.py:44-53,77-80); bounded to ~25 s
   train_check       N = 1, rank 0: three SGD steps on 4 frames -- losses of the fp32 and bf16 HIP plans next to the fp64 oracle's
@@ -45,7 +50,6 @@ sys.path.insert(0, REPO)
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MFMA_F32_PEAK_TFLOPS = 157.3   # dense fp32 MFMA peak (== fp32 vector peak)
 MFMA_H16_PEAK_TFLOPS = 2500.0  # dense bf16 / fp16 MFMA peak
-REFERENCE = "/root/reference"
 
 
 def parse_args():
@@ -54,11 +58,14 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=32, help="frames per GPU per step (BASELINE.json configs[1]: 32)")
-    ap.add_argument("--cpu-seconds", type=float, default=25.0, help="time budget of the host-CPU baseline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--profile-steps", type=int, default=10, help="instrumented steps for the per-kernel roofline")
-    ap.add_argument("--extra-steps", type=int, default=30, help="timed steps for each entry of `other_configs`; 0 disables")
-    ap.add_argument("--train-steps", type=int, default=20, help="timed train steps per plan (`train_step`, `train_step_bf16`); 0 disables")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the depth map of the last timed step to DIR/depth.npy (rank 0)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure the later windows, roofline, train steps, other "
+                                                         "configurations, host-CPU baseline and train check (the options below)")
+    ap.add_argument("--cpu-seconds", type=float, default=25.0, help="time budget of the host-CPU baseline (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the host-CPU baseline and the train check")
+    ap.add_argument("--profile-steps", type=int, default=10, help="instrumented steps for the per-kernel roofline (--full)")
+    ap.add_argument("--extra-steps", type=int, default=30, help="timed steps for each entry of `other_configs` (--full); 0 disables")
+    ap.add_argument("--train-steps", type=int, default=20, help="timed train steps per plan (`train_step`, `train_step_bf16`; --full); 0 disables")
     ap.add_argument("--grad-exchange", default="f32", choices=["f32", "bf16"], help="dtype of the data-parallel gradient all-reduce (bf16: 7.92 MB instead of 15.84 MB)")
     ap.add_argument("--only", default="", choices=["", "infer", "train_f32", "train_bf16", "f16", "bf16", "pruned_f16"],
                     help="run ONE configuration's timed loop and nothing else (one rocprofv3 invocation per configuration: tools/gpu_round.sh)")
@@ -269,50 +276,22 @@ def train_profile(teng, xs, tgts, stats, steps, mfma_peak_tflops, param_bytes, c
 
 # ------------------------------------------------------------------------------------------------------------------------------------
 def cpu_baseline(budget_s):
-    """The host-CPU yard-stick of BASELINE.md section 3: the reference's unmodified module (torchvision stub only) when /root/reference is
-    present, else the oracle's torch-functional restatement of it (the same ATen CPU kernels), fp32, eval + no_grad for inference,
-    L1Loss + SGD(0.01, 0.9, 1e-4) for the train step; warm-up then repeated timed runs, median (deploy/tx2_run_tvm.py:44-53,77-80)."""
+    """The host-CPU yard-stick of BASELINE.md section 3: the TorchScript traces of the reference's unmodified module that build() makes
+    where the reference is present, else the oracle's torch-functional restatement of it (the same ATen CPU kernels), fp32, eval + no_grad
+    for inference, L1Loss + SGD(0.01, 0.9, 1e-4) for the train step; warm-up then repeated timed runs, median (deploy/tx2_run_tvm.py:44-53,77-80)."""
     import torch
-    import types
     t_start = time.time()
-    kind, module, fwd = "port", None, None
-    if os.path.isdir(REFERENCE):
-        sys.dont_write_bytecode = True                 # importing the reference must not leave __pycache__ in its (read-only) tree
-        # the reference's own packages are called `models` / `imagenet` like the product's drop-ins: swap them in sys.modules for the
-        # duration of the import only (the reference's module objects stay alive through `module`)
-        names = ("torchvision", "torchvision.models", "models", "imagenet", "imagenet.mobilenet")
-        saved = {k: sys.modules.pop(k, None) for k in names}
+    kind, module = "port", None
+    # the traces of the reference's own module (oracle/make_ref_trace.py, git-ignored oracle/_ref/): the reference's operator graph on
+    # the same ATen CPU kernels, eager == traced bit for bit at trace time
+    traced = None
+    ev_p, tr_p = (os.path.join(REPO, "oracle", "_ref", "reference_module_%s.pt" % k) for k in ("eval", "train"))
+    if os.path.exists(ev_p) and os.path.exists(tr_p):
         try:
-            import importlib
-            stub = types.ModuleType("torchvision"); stub.models = types.ModuleType("torchvision.models")
-            sys.modules["torchvision"], sys.modules["torchvision.models"] = stub, stub.models     # only the ResNet classes use it
-            sys.path.insert(0, REFERENCE)
-            ref_models = importlib.import_module("models")
-            assert os.path.abspath(ref_models.__file__).startswith(REFERENCE)
-            torch.manual_seed(0)
-            module = ref_models.MobileNetSkipAdd((224, 224), pretrained=False)
+            traced = (torch.jit.load(ev_p), torch.jit.load(tr_p))
             kind = "reference"
         except Exception:
-            module = None
-        finally:
-            if REFERENCE in sys.path:
-                sys.path.remove(REFERENCE)
-            for k in names:
-                sys.modules.pop(k, None)
-                if saved[k] is not None:
-                    sys.modules[k] = saved[k]
-    traced = None
-    if module is None:
-        # the GPU boxes have no /root/reference: replay the TorchScript traces of the reference's own module that oracle/make_ref_trace.py
-        # made where the reference is present (oracle/_ref/, git-ignored, travels with the snapshot) -- the reference's operator graph on
-        # the same ATen CPU kernels, eager == traced bit for bit at trace time
-        ev_p, tr_p = (os.path.join(REPO, "oracle", "_ref", "reference_module_%s.pt" % k) for k in ("eval", "train"))
-        if os.path.exists(ev_p) and os.path.exists(tr_p):
-            try:
-                traced = (torch.jit.load(ev_p), torch.jit.load(tr_p))
-                kind = "reference"
-            except Exception:
-                traced = None
+            traced = None
     if traced is not None:
         class Traced:                                      # the two traces behind the small part of nn.Module's surface the timing loops use
             def __init__(self):
@@ -393,8 +372,7 @@ def cpu_baseline(budget_s):
     best = max(rows, key=lambda r: r["fps"])
     b32 = max([r for r in rows if r["batch"] == 32] or [best], key=lambda r: r["fps"])
     b1 = max([r for r in rows if r["batch"] == 1] or [best], key=lambda r: r["fps"])
-    what = ("TorchScript trace of /root/reference's models.MobileNetSkipAdd (oracle/make_ref_trace.py: the reference's own operator graph, eager == traced bit for bit)" if traced is not None
-            else "/root/reference models.MobileNetSkipAdd, unmodified (torchvision stub only)" if kind == "reference"
+    what = ("TorchScript trace of the reference's models.MobileNetSkipAdd (oracle/make_ref_trace.py: the reference's own operator graph, eager == traced bit for bit)" if traced is not None
             else "oracle/torch_ref.py (the ATen CPU conv / batch_norm / hardtanh / upsample / add kernels the reference dispatches to)")
     return {"value": best["fps"], "unit": "frames/s", "cores": threads, "kind": kind,
             "sample": "%s, fp32 eval + no_grad on %d of %d host threads: best of B in {1, 8, 32} x {contiguous, channels_last}, 2 warm-ups + median of "
@@ -442,7 +420,7 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus > 1 and world == 1 and "RANK" not in os.environ:
         self_launch(args)
-    import numpy as np  # noqa: F401
+    import numpy as np
     import torch
     if not torch.cuda.is_available():
         sys.exit("bench.py needs an MI355X: torch.cuda.is_available() is False (there is no CPU fallback)")
@@ -486,6 +464,7 @@ def main():
         return float(t.item())
 
     last_host_enqueue = [0.0]
+    last_output = [None]
 
     def time_forward(mod, xin, steps, warmup, fn=None):
         ring = xin if isinstance(xin, list) else None
@@ -508,6 +487,7 @@ def main():
             barrier()
         assert torch.isfinite(y).all()
         last_host_enqueue[0] = t_host
+        last_output[0] = y
         return max_over_ranks(elapsed)
 
     def make_train_engine(dtype):
@@ -601,13 +581,36 @@ def main():
             PREROLL += 20
     elapsed = time_forward(model, x_ring, args.steps, args.warmup)
     host_enqueue_ms = last_host_enqueue[0] / args.steps * 1e3
-    # The headline is the window above (the contract's K steps after W warm-up steps).  NWIN - 1 further windows of K steps each follow it
-    # back to back, untimed by the contract: they show whether the first window sat on a clock ramp (later windows faster), on the host
-    # (host_enqueue_ms_per_step close to ms_per_step) or on neither.
+    ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "depth.npy"), last_output[0].float().cpu().numpy())
+    n_kernels = sum(1 for st in eng.layer_stats(x) if st[1])
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "frames/sec (224x224) MobileNet-NNConv5dw-skipadd inference forward",
+            "value": round(world * args.batch * args.steps / elapsed, 1), "unit": "frames/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+            "host_enqueue_ms_per_step": round(host_enqueue_ms, 4),
+            "data": "synthetic (U[0,1) NYU-v2-shaped frames, random-init weights with calibrated BN statistics)",
+            "config": {"workload": "configs[1]: MobileNet-NNConv5(dw)+skipadd unpruned, batch=32 per GPU, 224x224 fp32 "
+                                   "inference forward, inputs resident in HBM", "batch_per_gpu": args.batch,
+                       "global_batch": world * args.batch, "parallelism": "frames sharded over %d GPU(s), no collective" % world,
+                       "kernels_per_step": n_kernels, "rccl_ranks": world if dist is not None else 0,
+                       "untimed_device_wakeup_steps_before_warmup": PREROLL, "input_batches_in_rotation": NRING},
+        }
+    if not args.full:
+        finish(dist, line)
+        return
+
+    # ---- --full: everything below is measured after the headline, in runs of its own ---------------------------------------------------
+    # NWIN - 1 further windows of K steps each follow the headline window back to back: they show whether the first window sat on a clock
+    # ramp (later windows faster).
     NWIN = 6
     windows = [round(elapsed / args.steps * 1e3, 4)] + [round(time_forward(model, x_ring, args.steps, 0) / args.steps * 1e3, 4) for _ in range(NWIN - 1)]
-    roof, whole, kernels, n_kernels = inference_profile(eng, x, args.profile_steps, MFMA_F32_PEAK_TFLOPS)
-    ms_per_step = elapsed / args.steps * 1e3
+    roof, whole, kernels, _ = inference_profile(eng, x, args.profile_steps, MFMA_F32_PEAK_TFLOPS)
     whole["frac_of_roofline"] = round(whole["roofline_bound_ms"] / ms_per_step, 4)
     whole["frac_of_fused_plan_bound"] = round(whole["fused_plan_bound_ms"] / ms_per_step, 4)
 
@@ -649,27 +652,16 @@ def main():
         extras.append({"config": "configs[0] on the GPU: unpruned, batch=1, fp32, hipGraph replay (latency; the reference publishes 5.6 ms for the PRUNED model on a Jetson TX2)",
                        "value": round(1 / dt, 1), "unit": "frames/s", "ms_per_step": round(dt * 1e3, 4), "dtype": "f32"})
 
-    line = None
     if rank == 0:
-        line = {
-            "metric": "frames/sec (224x224) MobileNet-NNConv5dw-skipadd inference forward",
-            "value": round(world * args.batch * args.steps / elapsed, 1), "unit": "frames/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "windows_ms_per_step": windows, "host_enqueue_ms_per_step": round(host_enqueue_ms, 4),
-            "data": "synthetic (U[0,1) NYU-v2-shaped frames, random-init weights with calibrated BN statistics)",
-            "config": {"workload": "configs[1]: MobileNet-NNConv5(dw)+skipadd unpruned, batch=32 per GPU, 224x224 fp32 "
-                                   "inference forward, inputs resident in HBM", "batch_per_gpu": args.batch,
-                       "global_batch": world * args.batch, "parallelism": "frames sharded over %d GPU(s), no collective" % world,
-                       "kernels_per_step": n_kernels, "rccl_ranks": world if dist is not None else 0,
-                       "untimed_device_wakeup_steps_before_warmup": PREROLL, "input_batches_in_rotation": NRING},
+        line.update({
+            "windows_ms_per_step": windows,
             "roofline": roof,
             "whole_step": whole,
             "kernels": kernels,
             "train_step": train,
             "train_step_bf16": train_bf16,
             "other_configs": extras,
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
             try:

@@ -8,8 +8,8 @@ TEST INFRASTRUCTURE; usage:  python -m oracle.make_ref_checkpoints [--full]
                                   closures build (imagenet/mobilenet.py:22-38), decoder units come from the reference's own
                                   `models.depthwise` / `models.pointwise` (models.py:61-75); `best_result` = a reference `metrics.Result`.
   tests/golden/ref_ckpt_tiny_io.npz           the input and the REFERENCE'S output for that instance (64 x 64, batch 2)
-  --full: tests/golden/_ref/ref_ckpt_{unpruned,pruned}.pth.tar + ref_ckpt_pruned_io.npz   (git-ignored: 16 MB / 5 MB; they travel to the GPU box
-                                  with the snapshot).  `unpruned` is the calibrated seed-0 model of make_golden.py, whose reference output is
+  --full: ONLY oracle/_ref/ref_ckpt_{unpruned,pruned}.pth.tar + ref_ckpt_pruned_io.npz   (build() makes them; git-ignored: 16 MB / 5 MB;
+                                  the committed files above are left alone).  `unpruned` is the calibrated seed-0 model of make_golden.py, whose reference output is
                                   the committed tests/golden/base_s0_out.npy; `pruned` has the published pruned widths.
 """
 import os
@@ -23,6 +23,7 @@ from oracle import make_golden
 from oracle.inputs import batch_variants
 
 GOLD = make_golden.GOLD
+FULL_DIR = os.path.join(make_golden.REPO, "oracle", "_ref")      # the full-size fixtures (--full)
 TINY = ((16, 56, 88, 120, 144, 72, 104, 40, 72, 88, 96, 128, 80, 112), (200, 72, 120, 56, 16, 1))     # multiples of 8, mostly not of 32
 PRUNED = ((16, 56, 88, 120, 144, 256, 408, 376, 272, 288, 296, 328, 480, 512), (200, 256, 120, 56, 16, 1))
 
@@ -75,11 +76,12 @@ def main():
     x = torch.rand(2, 3, 64, 64, generator=torch.Generator().manual_seed(32))
     with torch.no_grad():
         y = tiny(x)
-    torch.save({"epoch": 3, "best_result": best, "model": tiny}, os.path.join(GOLD, "ref_ckpt_tiny_pruned.pth.tar"))
-    np.savez(os.path.join(GOLD, "ref_ckpt_tiny_io.npz"), x=x.numpy(), y=y.numpy())
-    print("tiny pruned reference checkpoint:", os.path.getsize(os.path.join(GOLD, "ref_ckpt_tiny_pruned.pth.tar")), "bytes; output range", float(y.min()), float(y.max()))
-    if "--full" in sys.argv:
-        out = os.path.join(GOLD, "_ref")
+    if "--full" not in sys.argv:
+        torch.save({"epoch": 3, "best_result": best, "model": tiny}, os.path.join(GOLD, "ref_ckpt_tiny_pruned.pth.tar"))
+        np.savez(os.path.join(GOLD, "ref_ckpt_tiny_io.npz"), x=x.numpy(), y=y.numpy())
+        print("tiny pruned reference checkpoint:", os.path.getsize(os.path.join(GOLD, "ref_ckpt_tiny_pruned.pth.tar")), "bytes; output range", float(y.min()), float(y.max()))
+    else:
+        out = FULL_DIR
         os.makedirs(out, exist_ok=True)
         sample = torch.from_numpy(np.load(os.path.join(GOLD, "sample_rgb_u8.npy")).astype(np.float64) / 255.0).permute(2, 0, 1).float()[None]
         m = make_golden.calibrated(ref_models, 0, sample, "base")

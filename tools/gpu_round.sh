@@ -10,7 +10,8 @@ echo "== smoke"; timeout 300 python __graft_entry__.py smoke > $OUT/smoke.log 2>
 if [ -z "$2" ]; then echo "== pytest -m gpu"; timeout 1500 python -m pytest tests -m gpu -q -x --timeout 900 > $OUT/pytest_gpu.log 2>&1; echo "rc=$?"; tail -8 $OUT/pytest_gpu.log; fi
 echo "== bench: the driver's protocol (bench.py --gpus 1 --steps 20 --warmup 5), three fresh processes; the first is the archived bench line"
 bash tools/gpu_driver_protocol.sh $TAG 3
-cp $OUT/bench_driver_protocol_1.json $OUT/bench.json
+echo "== bench --full (roofline, train steps, other configurations, host-CPU baseline): the archived bench line"
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err; echo "rc=$?"
 python tools/show_bench.py $OUT/bench.json
 echo "== bf16 vs fp32 plan gradients at B = 32 (tools/bf16_grad_probe.py)"; timeout 300 python tools/bf16_grad_probe.py 32 2>&1 | tail -5 | tee $OUT/bf16_grad_probe.txt
 cd /tmp && export TMPDIR=/tmp
