@@ -127,19 +127,19 @@ typedef float fd_f32x16 __attribute__((ext_vector_type(16)));
 #define FD_ACT_RELU_ 1
 #define FD_ACT_RELU6_ 2
 
-// activation of the fused Conv-BN-act units: ReLU (models.py:67,74) or ReLU6 (imagenet/mobilenet.py:16-20)
+// activation of the fused Conv-BN-act units: ReLU (models.py:67,74) or ReLU6 (imagenet/mobilenet.py:16-20).  NaN propagates, as in F.relu / F.hardtanh:
+// IEEE-754-2019 maximum / minimum (gfx950: v_maximum3_f32 / v_minimum3_f32), not fmaxf / fmed3, which return the non-NaN operand and would scrub a NaN
+// into a plausible 0 (or 6)
+__device__ __forceinline__ float fd_relu_clamp(float v, float hi) { return __builtin_elementwise_minimum(__builtin_elementwise_maximum(v, 0.0f), hi); }
 template <int ACT>
 __device__ __forceinline__ float fd_act(float v)
 {
-    if (ACT == FD_ACT_RELU_) return fmaxf(v, 0.0f);
-#ifdef FD_EMU
-    if (ACT == FD_ACT_RELU6_) return fminf(fmaxf(v, 0.0f), 6.0f);
-#else
-    if (ACT == FD_ACT_RELU6_) return __builtin_amdgcn_fmed3f(v, 0.0f, 6.0f);     // one v_med3_f32 (same value for every non-NaN input)
-#endif
+    if (ACT == FD_ACT_RELU_) return __builtin_elementwise_maximum(v, 0.0f);      // one v_maximum3_f32 v, 0, 0
+    if (ACT == FD_ACT_RELU6_) return fd_relu_clamp(v, 6.0f);                       // v_maximum3_f32 + v_minimum3_f32
     return v;
 }
-// the same on a value that comes out of inline asm (fd_dot2_acc): fmaxf / fmed3 would first canonicalise it (a second v_max_f32 per value)
+// the same on a value that comes out of inline asm (fd_dot2_acc): the builtins would first canonicalise it (a second VALU per value).  The callers have
+// passed the accumulators through fd_dot2_done (the DOT read hazard) before this reads them.
 template <int ACT>
 __device__ __forceinline__ float fd_act_raw(float v)
 {
@@ -147,8 +147,8 @@ __device__ __forceinline__ float fd_act_raw(float v)
     return fd_act<ACT>(v);
 #else
     float r = v;
-    if (ACT == FD_ACT_RELU_) asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(v));
-    if (ACT == FD_ACT_RELU6_) { const float six = 6.0f; asm("v_med3_f32 %0, %1, 0, %2" : "=v"(r) : "v"(v), "s"(six)); }
+    if (ACT == FD_ACT_RELU_) asm("v_maximum3_f32 %0, %1, 0, 0" : "=v"(r) : "v"(v));
+    if (ACT == FD_ACT_RELU6_) { const float six = 6.0f; asm("v_maximum3_f32 %0, %1, 0, 0\n\tv_minimum3_f32 %0, %0, %2, %2" : "=&v"(r) : "v"(v), "s"(six)); }
     return r;
 #endif
 }
@@ -174,15 +174,16 @@ typedef unsigned short fd_u16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ float fd_bf16_to_f32(unsigned short b) { return __builtin_bit_cast(float, (unsigned)b << 16); }
 #ifdef FD_EMU
 __device__ __forceinline__ unsigned short fd_f32_to_bf16(float f)
-{   // round to nearest even (NaN handling is not needed on this path: inputs are finite)
+{   // round to nearest even; a NaN stays a NaN of the same sign (quieted), as gfx950's v_cvt_pk_bf16_f32 keeps it
     unsigned u = __builtin_bit_cast(unsigned, f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40u);
     u += 0x7fffu + ((u >> 16) & 1u);
     return (unsigned short)(u >> 16);
 }
 // two values -> one 32-bit word (low half = a)
 __device__ __forceinline__ unsigned fd_f32x2_to_bf16x2(float a, float b) { return (unsigned)fd_f32_to_bf16(a) | ((unsigned)fd_f32_to_bf16(b) << 16); }
 #else
-// gfx950 converts in hardware (v_cvt_pk_bf16_f32, round to nearest even: the same value as the integer formula above for every finite input)
+// gfx950 converts in hardware (v_cvt_pk_bf16_f32, round to nearest even: the same value as the emulator's formula above for every input, NaN included)
 __device__ __forceinline__ unsigned short fd_f32_to_bf16(float f) { return __builtin_bit_cast(unsigned short, (__bf16)f); }
 __device__ __forceinline__ unsigned fd_f32x2_to_bf16x2(float a, float b)
 {
@@ -527,31 +528,44 @@ __device__ __forceinline__ unsigned fd_pair_sum(fd_bf16, unsigned a, unsigned b)
 //     backward (sums of G, G * xhat):   |v| < 2^-32 -> frac 80,   2^-32 <= |v| < 2^-8 -> frac 56,   |v| >= 2^-8  -> frac 32
 // so a 24-bit mantissa lands at bit positions < 2^48 of an int64 and 2^14 partials fit with room to spare, across 72 binary orders of magnitude
 // (below the lowest bin's 2^-33 * 2^-frac0 ... values lose low bits: < 2^-89 (forward) / 2^-113 (backward) each; fp32 denormals count as 0; above 2^40
-// (forward) / 2^16 (backward) per PARTIAL the value saturates -- a diverged network).  The total of a column is then the EXACT sum of the fp32 partials,
-// reconstructed in double from the three bins (fd_stat_total).
+// (forward) / 2^16 (backward) per PARTIAL the value saturates -- a diverged network).  A column takes at most FD_STAT_MAX_PARTIALS = 2^15 partials over all
+// its rows (fd_train_impl.h: the plan's headroom check), so neither a row slot nor the cross-row total in fd_stat_total can reach 2^63 and wrap: each bin's
+// total is the EXACT sum of its fp32 partials, rounded once to double; the column total is the sum of the three bins in double.
+// An Inf / NaN partial (a diverged step or a non-finite input) instead sets the column's POISON FLAG (one more [2][cs] slot behind the rows, an atomic OR:
+// idempotent, so any number of such partials in any order and any row slicing leaves the same flag), and fd_stat_total returns NaN for the column,
+// as nn.BatchNorm2d's batch statistics would be.
 // One address takes an atomic every ~22 ns whatever the scope (tools/microbench/stat_atomics.hip, MI355X: 6272 workgroups x 128 columns into ONE row
 // 135 us, into 8 rows 18 us), so a unit's partials are dealt to nr rows (a power of two <= 16, chosen by the plan so that an address sees <= ~128
 // adds (FD_STAT_ADDS_PER_ROW, fd_train_plan.h): row = workgroup number & (nr - 1)) and the consumer adds the nr x 3 integers of a column.
-// Layout of a unit's rows: int64 [nr][FD_STAT_BINS][2][cs]  (2 = first / second sum; cs = channel pitch >= C, a multiple of 16: the memory side
-// serialises atomics per 128-byte LINE and instruction, so no two (row, bin, sum) slots share a line).  The plan zeroes all rows of a step with one memset.
+// Layout of a unit's rows: int64 [nr][FD_STAT_BINS][2][cs], then the poison flags int64 [2][cs]  (2 = first / second sum; cs = channel pitch >= C, a
+// multiple of 16: the memory side serialises atomics per 128-byte LINE and instruction, so no two (row, bin, sum) slots share a line).  The plan zeroes all
+// rows of a step with one memset.
 #define FD_STAT_BINS 3
-#define FD_STAT_POISON (1LL << 62)      /* added to the highest bin by an Inf / NaN partial */
 #define FD_STAT_MAX_ROWS 16
+#define FD_STAT_MAX_PARTIALS (1L << 15)      /* per column, all rows together: 2^15 x (< 2^48) < 2^63 */
 #define FD_STAT_FWD 0
 #define FD_STAT_BWD 1
 struct fd_stat_rows { long long *rows; int nr, cs; };    // nr: power of two; cs: channel pitch of the rows (>= C; >= 16 so that every [row][bin][sum] slot starts its own 128-byte line)
 #ifdef FD_EMU
-inline void fd_atomic_add_i64(long long *p, long long v) { *p += v; }
+// (two's-complement wrap spelled out: a signed overflow would be undefined behaviour in C++, the hardware atomic wraps)
+inline void fd_atomic_add_i64(long long *p, long long v) { *p = (long long)((unsigned long long)*p + (unsigned long long)v); }
+inline void fd_atomic_or_i64(long long *p, long long v) { *p |= v; }
 #else
 __device__ __forceinline__ void fd_atomic_add_i64(long long *p, long long v)
 {
     (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // result unused: a no-return global_atomic_add_x2
+}
+__device__ __forceinline__ void fd_atomic_or_i64(long long *p, long long v)
+{
+    (void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // a no-return global_atomic_or_x2
 }
 #endif
 template <int DIR> struct fd_stat_fmt {
     static constexpr int lo = DIR == FD_STAT_FWD ? -8 : -32, hi = DIR == FD_STAT_FWD ? 16 : -8;     // bin boundaries (binary exponents)
     static constexpr int f0 = DIR == FD_STAT_FWD ? 56 : 80, f1 = f0 - 24, f2 = f0 - 48;
 };
+// the poison flag of column c (sum `which`) of a unit with nr rows at channel pitch cs
+__device__ __forceinline__ long fd_stat_flag_index(int nr, int cs, int which, int c) { return ((long)nr * FD_STAT_BINS * 2 + which) * cs + c; }
 // adds the fp32 partial v of column c (sum `which`) of workgroup number blk to the unit's rows
 template <int DIR>
 __device__ __forceinline__ void fd_stat_add(const fd_stat_rows &d, long blk, int /*C*/, int which, int c, float v)
@@ -560,8 +574,8 @@ __device__ __forceinline__ void fd_stat_add(const fd_stat_rows &d, long blk, int
     const unsigned u = __builtin_bit_cast(unsigned, v);
     int e = (int)((u >> 23) & 255u) - 127;
     if (e == -127) return;                                  // +-0 and denormals: nothing to add
-    if (e == 128) {                                         // Inf / NaN partial (a diverged step): POISON the column -- fd_stat_total returns NaN, as nn.BatchNorm2d's
-        fd_atomic_add_i64(d.rows + ((((long)(blk & (d.nr - 1)) * FD_STAT_BINS + 2) * 2 + which) * d.cs + c), FD_STAT_POISON);   // statistics would be
+    if (e == 128) {                                         // Inf / NaN partial: poison the column (fd_stat_total returns NaN)
+        fd_atomic_or_i64(d.rows + fd_stat_flag_index(d.nr, d.cs, which, c), 1);
         return;
     }
     const int bin = e < F::lo ? 0 : (e < F::hi ? 1 : 2);
@@ -574,7 +588,8 @@ __device__ __forceinline__ void fd_stat_add(const fd_stat_rows &d, long blk, int
     if (iv == 0) return;
     fd_atomic_add_i64(d.rows + ((((long)(blk & (d.nr - 1)) * FD_STAT_BINS + bin) * 2 + which) * d.cs + c), iv);
 }
-// the exact total of column c (sum `which`) over the partials in rows r0, r0 + rstep, ... < nr (r0 = 0, rstep = 1: of the whole unit), as a double
+// the exact total of column c (sum `which`) over the partials in rows r0, r0 + rstep, ... < nr (r0 = 0, rstep = 1: of the whole unit), as a double;
+// NaN if the column is poisoned (checked by the r0 = 0 slice: a caller that splits the rows into slices adds the slices' doubles)
 template <int DIR>
 __device__ __forceinline__ double fd_stat_total(const long long *__restrict__ rows, int nr, int C /* channel pitch */, int which, int c, int r0, int rstep)
 {
@@ -584,9 +599,9 @@ __device__ __forceinline__ double fd_stat_total(const long long *__restrict__ ro
         const long long *p = rows + (((long)r * FD_STAT_BINS) * 2 + which) * C + c;
         a0 += p[0]; a1 += p[2 * (long)C]; a2 += p[4 * (long)C];
     }
-    // (a poisoned column: the highest bin holds at most 2^14 partials below 2^48 in magnitude, i.e. |a2| < 2^62 unless FD_STAT_POISON = 2^62 was added)
-    if (a2 >= FD_STAT_POISON / 2 || a2 <= -(FD_STAT_POISON / 2)) return __builtin_nan("");
-    return ldexp((double)a0, -F::f0) + ldexp((double)a1, -F::f1) + ldexp((double)a2, -F::f2);
+    // (no wrap: the plan admits at most FD_STAT_MAX_PARTIALS partials of < 2^48 per column, so |a| < 2^63)
+    const double t = ldexp((double)a0, -F::f0) + ldexp((double)a1, -F::f1) + ldexp((double)a2, -F::f2);
+    return (r0 == 0 && rows[fd_stat_flag_index(nr, C, which, c)] != 0) ? __builtin_nan("") : t;
 }
 
 // ---- device-coherent accesses ("last arriver" reductions: stream-K partial tiles, fused two-level reductions of the train step) ----

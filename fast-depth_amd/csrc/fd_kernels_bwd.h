@@ -13,7 +13,7 @@
 //   The conv-backward kernels form dz_i ON LOAD from (G_i, z_i) and re-create their forward input
 //   a_{i-1} = act(z_{i-1}*s+t) (+ nearest-x2 / skip composition) on load as well: no normalised, activated,
 //   upsampled or BN-backward tensor is ever written to HBM.
-//   Activation masks are strict (ReLU: y > 0; ReLU6: 0 < y < 6), as torch's threshold/hardtanh backward.
+//   Activation masks: ReLU zeroes the gradient where y <= 0 (a NaN y passes, as torch's threshold_backward), ReLU6 passes it where 0 < y < 6 (fd_actmask).
 // All reductions are two-stage with a fixed summation order (deterministic).
 #pragma once
 #include "fd_kernels_train.h"
@@ -33,9 +33,34 @@ template <typename V> __device__ __forceinline__ V fd_dz4(V g, V z, V cA, V c1, 
 template <int ACT>
 __device__ __forceinline__ float fd_actmask(float y)
 {
-    if (ACT == FD_ACT_RELU_) return y > 0.0f ? 1.0f : 0.0f;
+    // at a NaN pre-activation: ReLU passes the gradient (torch's threshold_backward: zero only where y <= 0); ReLU6 blocks it, as the vectorised
+    // body of torch's CPU hardtanh_backward does (its scalar tail, the last few elements of a tensor, would pass it)
+    if (ACT == FD_ACT_RELU_) return y <= 0.0f ? 0.0f : 1.0f;
     if (ACT == FD_ACT_RELU6_) return (y > 0.0f && y < 6.0f) ? 1.0f : 0.0f;
     return 1.0f;
+}
+// the gradient g through the activation at pre-activation y, as a SELECT (torch's threshold_backward / hardtanh_backward): a multiplication by the 0 / 1
+// mask would let a NaN / Inf gradient through where the mask blocks it (NaN * 0), the same instruction count
+template <int ACT>
+__device__ __forceinline__ float fd_actgate(float g, float y)
+{
+    if (ACT == FD_ACT_RELU_) return y <= 0.0f ? 0.0f : g;
+    if (ACT == FD_ACT_RELU6_) return (y > 0.0f && y < 6.0f) ? g : 0.0f;
+    return g;
+}
+template <int ACT>
+__device__ __forceinline__ fd_f32x4 fd_actgate4(fd_f32x4 g, fd_f32x4 y)
+{
+    fd_f32x4 r = {fd_actgate<ACT>(g.x, y.x), fd_actgate<ACT>(g.y, y.y), fd_actgate<ACT>(g.z, y.z), fd_actgate<ACT>(g.w, y.w)};
+    return r;
+}
+template <int ACT>
+__device__ __forceinline__ fd_f32x8 fd_actgate4(fd_f32x8 g, fd_f32x8 y)
+{
+    fd_f32x8 r;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = fd_actgate<ACT>(g[j], y[j]);
+    return r;
 }
 template <int ACT>
 __device__ __forceinline__ fd_f32x4 fd_actmask4(fd_f32x4 y)
@@ -368,7 +393,7 @@ fd_head_bwd_reduce_f32(const float *__restrict__ dpred, const float *__restrict_
         } else {
             d = dpred[p];
         }
-        const float gv = d * fd_actmask<ACT>(y);
+        const float gv = fd_actgate<ACT>(d, y);
         g[p] = gv;
         dy += gv;
         dyx = fmaf(gv, (z - st_mu) * st_is, dyx);
@@ -407,7 +432,7 @@ fd_head_bwd(const float *__restrict__ g, const float *__restrict__ zlow, const f
                 const float dz = fd_dz(g[p], zlow[p], cA, c1, cM, c2);
                 const fd_f32x4 z = fd_ld4(zin + p * Cin + c);
                 const fd_f32x4 y = z * s4 + t4;
-                const fd_f32x4 gi = fd_round4(T{}, fd_actmask4<ACT_IN>(y) * (w4 * dz));
+                const fd_f32x4 gi = fd_round4(T{}, fd_actgate4<ACT_IN>(w4 * dz, y));
                 fd_st4(g_in + p * Cin + c, gi);
                 sg += gi; sgx += gi * ((z - m4) * i4);
                 sw += fd_act4<ACT_IN>(y) * dz;
@@ -559,7 +584,7 @@ fd_pw_dgrad_f32_body(const float *__restrict__ G, const float *__restrict__ Z, c
                 const float z = e_z[r];
                 float v = acc[r];
                 if (ADD_SG) v += e_sg[r];
-                v *= fd_actmask<ACT_IN>(z * sc + sh);
+                v = fd_actgate<ACT_IN>(v, z * sc + sh);
                 Gin[row * K + col] = v;
                 s += v; q = fmaf(v, (z - mu) * is, q);
             }
@@ -847,7 +872,7 @@ fd_dw_dgrad_body(const T *__restrict__ G, const T *__restrict__ Z, const float *
                 const long o = fd_nhwc(n, Hin, gy, Win, gx, C, cg);
                 vec v = acc[j];
                 if (ADD_SG) v += sgv[j];
-                v = LN::round(v * fd_actmask4<ACT_IN>(z[j] * sc + sh));
+                v = LN::round(fd_actgate4<ACT_IN>(v, z[j] * sc + sh));
                 LN::st(Gin + o, v);
                 ssum += v; ssx += v * ((z[j] - mu) * is);
             }
@@ -863,7 +888,7 @@ fd_dw_dgrad_body(const T *__restrict__ G, const T *__restrict__ Z, const float *
             if (ADD_SG) sgv = LN::ld(SG + o);
             vec v = din_at(iy, ix);
             if (ADD_SG) v += sgv;
-            v = LN::round(v * fd_actmask4<ACT_IN>(z * sc + sh));
+            v = LN::round(fd_actgate4<ACT_IN>(v, z * sc + sh));
             LN::st(Gin + o, v);
             ssum += v; ssx += v * ((z - mu) * is);
         }
@@ -908,7 +933,7 @@ fd_dw_dgrad_body(const T *__restrict__ G, const T *__restrict__ Z, const float *
                 if (to_skip) continue;
             }
             vec v = (d00 + d01) + (d10 + d11);
-            v = LN::round(v * fd_actmask4<ACT_IN>(z * sc + sh));
+            v = LN::round(fd_actgate4<ACT_IN>(v, z * sc + sh));
             LN::st(Gin + ol, v);
             ssum += v; ssx += v * ((z - mu) * is);
         }
@@ -1354,7 +1379,7 @@ fd_dw_bwd1_body(const T *__restrict__ G, const T *__restrict__ Z, const float *_
                 const long o = fd_nhwc(n, Hin, gy, Win, gx, C, cg);
                 vec v = acc[j];
                 if (ADD_SG) v += sgv[j];
-                v = LN::round(v * fd_actmask4<ACT_IN>(z[j] * sc + sh));
+                v = LN::round(fd_actgate4<ACT_IN>(v, z[j] * sc + sh));
                 LN::st(Gin + o, v);
                 ssum += v; ssx += v * ((z[j] - mu) * is);
             }
@@ -1370,7 +1395,7 @@ fd_dw_bwd1_body(const T *__restrict__ G, const T *__restrict__ Z, const float *_
             if (ADD_SG) sgv = LN::ld(SG + o);
             vec v = din_at(iy, ix);
             if (ADD_SG) v += sgv;
-            v = LN::round(v * fd_actmask4<ACT_IN>(z * sc + sh));
+            v = LN::round(fd_actgate4<ACT_IN>(v, z * sc + sh));
             LN::st(Gin + o, v);
             ssum += v; ssx += v * ((z - mu) * is);
         }
@@ -1415,7 +1440,7 @@ fd_dw_bwd1_body(const T *__restrict__ G, const T *__restrict__ Z, const float *_
                 if (to_skip) continue;
             }
             vec v = (d00 + d01) + (d10 + d11);
-            v = LN::round(v * fd_actmask4<ACT_IN>(z * sc + sh));
+            v = LN::round(fd_actgate4<ACT_IN>(v, z * sc + sh));
             LN::st(Gin + ol, v);
             ssum += v; ssx += v * ((z - mu) * is);
         }
@@ -1550,8 +1575,8 @@ fd_dw3s2_dgrad_rows(const T *__restrict__ G, const T *__restrict__ Z, const floa
         fd_f32x4 v0 = dA * wA[1] + dB * wB[1];
         fd_f32x4 v1 = (dA * wA[2] + dB * wB[2]) + (nA * wA[0] + nB * wB[0]);
         if (ADD_SG) { v0 += g0; v1 += g1; }
-        v0 = fd_round4(T{}, v0 * fd_actmask4<ACT_IN>(z0 * sc + sh));
-        v1 = fd_round4(T{}, v1 * fd_actmask4<ACT_IN>(z1 * sc + sh));
+        v0 = fd_round4(T{}, fd_actgate4<ACT_IN>(v0, z0 * sc + sh));
+        v1 = fd_round4(T{}, fd_actgate4<ACT_IN>(v1, z1 * sc + sh));
         if (live) {
             fd_st4(Gin + o0, v0); fd_st4(Gin + o1, v1);
             ssum += v0; ssx += v0 * ((z0 - mu) * is);

@@ -78,16 +78,16 @@ __device__ __forceinline__ void fd_dw5_make_pairs(fd_bf16, const unsigned (&raw)
         pair[p][1] = fd_f32x2_to_bf16x2(__builtin_bit_cast(float, e & 0xffff0000u) + l1, __builtin_bit_cast(float, o & 0xffff0000u) + l1);
     }
 }
-// two activated fp32 outputs (adjacent channels) -> one word of the storage type.  ReLU commutes with the rounding and is one packed signed-integer
-// maximum on the packed word afterwards (sign-magnitude: a negative value is a negative int16, +-0 and positives are unchanged): v_pk_max_i16 for two
-// values instead of a 4-cycle v_max_f32 for each.
+// two activated fp32 outputs (adjacent channels) -> one word of the storage type.  fp16 ReLU commutes with the rounding and is one packed NaN-propagating
+// maximum on the packed word afterwards (v_pk_maximum3_f16 for two values instead of a v_maximum3_f32 for each).  bf16 has no packed maximum: the ReLU
+// runs on the fp32 values (a signed-integer maximum on the bit pattern, the earlier form, turned a NaN with its sign bit set into +0).
 template <typename T, int ACT>
 __device__ __forceinline__ unsigned fd_dw5_pack_act(float a, float b)
 {
-    if (ACT == FD_ACT_RELU_) {
-        typedef short fd_s16x2 __attribute__((ext_vector_type(2)));
-        const fd_s16x2 v = __builtin_bit_cast(fd_s16x2, fd_pack2(T{}, a, b)), z = {0, 0};
-        return __builtin_bit_cast(unsigned, __builtin_elementwise_max(v, z));
+    if constexpr (ACT == FD_ACT_RELU_ && std::is_same<T, fd_half>::value) {
+        typedef _Float16 fd_h16x2 __attribute__((ext_vector_type(2)));
+        const fd_h16x2 v = __builtin_bit_cast(fd_h16x2, fd_pack2(T{}, a, b)), z = {(_Float16)0.0f, (_Float16)0.0f};
+        return __builtin_bit_cast(unsigned, __builtin_elementwise_maximum(v, z));
     }
     return fd_pack2(T{}, fd_act_raw<ACT>(a), fd_act_raw<ACT>(b));
 }

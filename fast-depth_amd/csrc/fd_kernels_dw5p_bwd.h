@@ -181,7 +181,7 @@ fd_dw5_dgrad_rows_body(const fd_dw5_bwd_args<T> &a, float *red, const float *s_c
 #pragma unroll
                 for (int jl = 0; jl < 2; ++jl) {
                     const float z0 = fd_w16_lo(T{}, lo_now[jl]), z1 = fd_w16_hi(T{}, lo_now[jl]);
-                    const unsigned packed = fd_pack2(T{}, lacc[jl][0] * fd_actmask<ACT1>(fmaf(z0, s1[0], t1[0])), lacc[jl][1] * fd_actmask<ACT1>(fmaf(z1, s1[1], t1[1])));
+                    const unsigned packed = fd_pack2(T{}, fd_actgate<ACT1>(lacc[jl][0], fmaf(z0, s1[0], t1[0])), fd_actgate<ACT1>(lacc[jl][1], fmaf(z1, s1[1], t1[1])));
                     fd_buf_st32(r_gl, lo0, (unsigned)(y >> 1) * rowl + (unsigned)jl * pxb, packed);
                     const float g0 = fd_w16_lo(T{}, packed), g1 = fd_w16_hi(T{}, packed);      // statistics of the stored (rounded) gradient
                     sg0 += g0; sg1 += g1;
@@ -672,7 +672,7 @@ fd_dw3_dgrad_rows_body(const fd_dw3_bwd_args<T> &a, float *red, const float *s_c
                             d1 = fmaf(win[(ph + 1 + ky) % 3][j + kx][1], wf[ky][kx][1], d1);
                         }
                     const float z0 = fd_w16_lo(T{}, zi[j]), z1 = fd_w16_hi(T{}, zi[j]);
-                    const unsigned packed = fd_pack2(T{}, d0 * fd_actmask<ACT1>(fmaf(z0, s1[0], t1[0])), d1 * fd_actmask<ACT1>(fmaf(z1, s1[1], t1[1])));
+                    const unsigned packed = fd_pack2(T{}, fd_actgate<ACT1>(d0, fmaf(z0, s1[0], t1[0])), fd_actgate<ACT1>(d1, fmaf(z1, s1[1], t1[1])));
                     if (xs + j < W) {
                         fd_buf_st32(r_gi, so[1 + j], (unsigned)y * rowb, packed);
                         const float g0 = fd_w16_lo(T{}, packed), g1 = fd_w16_hi(T{}, packed);
@@ -999,7 +999,7 @@ fd_dw3s2_bwd_rows(const fd_dw3s2_bwd_args<T> a)
                     }
                     if (ADD_SG) { d[0] += fd_w16_lo(T{}, sgr[rr][i]); d[1] += fd_w16_hi(T{}, sgr[rr][i]); }
                     const float z0 = fd_w16_lo(T{}, zraw[rr][i]), z1 = fd_w16_hi(T{}, zraw[rr][i]);
-                    const unsigned packed = fd_pack2(T{}, d[0] * fd_actmask<ACT1>(fmaf(z0, s1[0], t1[0])), d[1] * fd_actmask<ACT1>(fmaf(z1, s1[1], t1[1])));
+                    const unsigned packed = fd_pack2(T{}, fd_actgate<ACT1>(d[0], fmaf(z0, s1[0], t1[0])), fd_actgate<ACT1>(d[1], fmaf(z1, s1[1], t1[1])));
                     if (ox0 + m < Wo) {
                         fd_buf_st32(r_gi, si[1 + i], (unsigned)(2 * oy + rr) * rowi, packed);
                         const float g0 = fd_w16_lo(T{}, packed), g1 = fd_w16_hi(T{}, packed);

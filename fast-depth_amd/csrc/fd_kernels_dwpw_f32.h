@@ -279,8 +279,8 @@ fd_dwpw_f32(const float *__restrict__ in, const float *__restrict__ skip, const 
             }
             if (g == 3 && head_ok) {
                 float v = head_v + head_b;
-                if (hd.act >= 1) v = fmaxf(v, 0.0f);
-                if (hd.act == 2) v = fminf(v, 6.0f);
+                if (hd.act == 1) v = fd_act<FD_ACT_RELU_>(v);
+                if (hd.act == 2) v = fd_act<FD_ACT_RELU6_>(v);
                 if (hd.up) {
                     const fd_f32x2 vv = {v, v};
                     *reinterpret_cast<fd_f32x2 *>(hd.y + head_off) = vv;

@@ -240,8 +240,8 @@ fd_pw_gemm16_h16(const T *__restrict__ A, const T *__restrict__ Wt, const float 
                         for (int kx = 0; kx < KD; ++kx) a4 += fd_ld4(p0 + (ky * PW + kx) * OP) * wv[ky * KD + kx];
                 }
                 fd_f32x4 r4;
-                r4.x = fminf(fmaxf(a4.x, 0.0f), fz.hi); r4.y = fminf(fmaxf(a4.y, 0.0f), fz.hi);
-                r4.z = fminf(fmaxf(a4.z, 0.0f), fz.hi); r4.w = fminf(fmaxf(a4.w, 0.0f), fz.hi);
+                r4.x = fd_relu_clamp(a4.x, fz.hi); r4.y = fd_relu_clamp(a4.y, fz.hi);
+                r4.z = fd_relu_clamp(a4.z, fz.hi); r4.w = fd_relu_clamp(a4.w, fz.hi);
                 fd_st4(dw_out + ((f0 + fr) * HWo + op) * N + c, r4);
                 ox += dx; oy += dy;
                 if (ox >= Wo) { ox -= Wo; ++oy; }

@@ -214,7 +214,7 @@ fd_pw_gemm_h16_body(const T *__restrict__ A, const T *__restrict__ Wt, const flo
             if (p < M) {
                 float acc1 = hd.b[0];
                 for (int c = 0; c < N; ++c) acc1 = fmaf(fd_ld1(tile + lane * 40 + c), hd.w[c], acc1);
-                const float v = hd.act == 2 ? fminf(fmaxf(acc1, 0.0f), 6.0f) : (hd.act == 1 ? fmaxf(acc1, 0.0f) : acc1);
+                const float v = hd.act == 2 ? fd_act<FD_ACT_RELU6_>(acc1) : (hd.act == 1 ? fd_act<FD_ACT_RELU_>(acc1) : acc1);
                 if (!hd.up) hd.y[p] = v;
                 else {
                     const int ox = (int)(p % hd.w_);

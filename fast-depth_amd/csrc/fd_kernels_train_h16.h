@@ -408,7 +408,7 @@ fd_pw_dgrad_h16_body(const T *__restrict__ DZ, const T *__restrict__ Wtt, const 
                         for (int j = 0; j < 8; ++j) v[j] += g[j];
                     }
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] *= fd_actmask<ACT_IN>(fmaf(z[j], sc[j], sh[j]));
+                    for (int j = 0; j < 8; ++j) v[j] = fd_actgate<ACT_IN>(v[j], fmaf(z[j], sc[j], sh[j]));
                     const fd_u16x8 packed = fd_pack8(T{}, v);
                     fd_st8(Gin + grow * K + gcol, packed);
                     fd_unpack8(T{}, packed, v);                   // statistics of the stored (rounded) gradient

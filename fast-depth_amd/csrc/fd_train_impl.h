@@ -434,9 +434,10 @@ int fd_train_plan_create(const fd_layer_desc *layers, int32_t n_layers, int32_t 
         if ((long)L.in_h * L.in_w >= (1L << 24) || d.cin >= (1 << 24) || d.cout >= (1 << 24) || (double)L.in_h * L.in_w * std::max(d.cin, d.cout) >= 4294967296.0)
             FD_BAD("layer %d: a %dx%d map with %d channels exceeds the kernels' 32-bit within-image addressing", i, L.in_h, L.in_w, std::max(d.cin, d.cout));
         L.M = (long)batch * L.out_h * L.out_w;
-        // statistics rows (fd_device.h): a 64-bit bin holds 2^14 partials of < 2^48 each with room to spare and a unit adds at most one partial per 64 stored
-        // pixels and channel -- larger batches would let the cross-row total wrap silently: rejected instead
-        if (ceil_div(L.M, 64) > (1L << 14) * FD_STAT_MAX_ROWS) FD_BAD("layer %d: %ld stored pixels per channel exceed the statistics rows' headroom (%d rows x 2^14 partials of 64 pixels)", i, L.M, FD_STAT_MAX_ROWS);
+        // statistics rows (fd_device.h): the int64 total of a column is exact for up to FD_STAT_MAX_PARTIALS partials of < 2^48 each and a unit adds at most one
+        // partial per 64 stored pixels and channel -- larger batches would let the total wrap silently: rejected instead (2^21 pixels per
+        // channel: batch 167 at 224 x 224)
+        if (ceil_div(L.M, 64) > FD_STAT_MAX_PARTIALS) FD_BAD("layer %d: %ld stored pixels per channel exceed the statistics rows' headroom (%ld partials of 64 pixels)", i, L.M, (long)FD_STAT_MAX_PARTIALS);
         L.z_elems = (size_t)L.M * d.cout;
         L.n_stat = (double)L.M;
         L.n_unbiased = (L.head && d.upsample) ? 4.0 * (double)L.M : (double)L.M;

@@ -146,7 +146,7 @@ inline int stat_nr(long nblk)
     return nr;
 }
 inline int stat_pitch(int C) { return (C + 15) / 16 * 16; }      // channel pitch of a unit's rows: every [row][bin][sum] slot starts its own 128-byte line
-inline size_t stat_rows_bytes(int nr, int C) { return (size_t)nr * FD_STAT_BINS * 2 * stat_pitch(C) * sizeof(long long); }
+inline size_t stat_rows_bytes(int nr, int C) { return ((size_t)nr * FD_STAT_BINS * 2 + 2) * stat_pitch(C) * sizeof(long long); }     // (+ the poison flags: fd_device.h)
 inline long long *stat_ptr(fd_train_plan *p, size_t off) { return reinterpret_cast<long long *>(p->ws + off); }
 // this unit's forward rows as its producer kernel sees them
 inline fd_stat_rows fwd_rows(fd_train_plan *p, const TLayer &L) { return fd_stat_rows{stat_ptr(p, L.sf_off), L.nr_f, stat_pitch(L.d.cout)}; }

@@ -38,5 +38,20 @@ def _build(force):
     return OUT
 
 
+def build_stat_shim():
+    """tests/hipemu/_build/libfd_stat_shim.so: stat_shim.cpp (fd_stat_add / fd_stat_total of fd_device.h) with the emulator's flags."""
+    os.makedirs(OUT_DIR, exist_ok=True)
+    out = os.path.join(OUT_DIR, "libfd_stat_shim.so")
+    src = os.path.join(HERE, "stat_shim.cpp")
+    deps = [src, os.path.join(HERE, "hipemu.h"), os.path.join(CSRC, "fd_device.h")]
+    import fcntl
+    with open(os.path.join(OUT_DIR, ".lock"), "w") as lk:
+        fcntl.flock(lk, fcntl.LOCK_EX)
+        if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+            subprocess.check_call([CLANG, "-x", "c++", "-std=c++17", "-O2", "-fPIC", "-shared", "-DFD_EMU", "-I", HERE, "-I", CSRC, "-Wall",
+                                   "-Wno-unused-function", "-Wno-unused-variable", "-Wno-psabi", "-Wno-comment", "-mavx2", src, "-o", out])
+    return out
+
+
 if __name__ == "__main__":
     print(build(force=True))

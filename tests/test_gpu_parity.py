@@ -485,3 +485,27 @@ def test_16bit_head_fusion_and_rows8_match_the_separate_kernels(pruned):
         assert torch.equal(y, y_rows4), dt
         assert harness.rel_err(y.cpu().numpy(), y_sep_head.cpu().numpy()) < (5e-3 if dt == torch.float16 else 4e-2), dt   # (NO_EPILOGUE_FUSION also un-fuses the 14x14 pairs: storage-type rounding)
         assert bool(torch.isfinite(y).all())
+
+
+@pytest.mark.parametrize("name,pruned,dtype", [("f32", False, torch.float32), ("f16", False, torch.float16), ("bf16", False, torch.bfloat16),
+                                               ("pruned_f16", True, torch.float16)])
+def test_nonfinite_inputs_propagate_like_reference_full_size(name, pruned, dtype):
+    """224 x 224, batch 4, default plans: one +NaN / -NaN / +Inf / -Inf pixel at a corner, an edge or the centre, an all-NaN frame and clean frames.
+    The exact non-finite mask against torch_ref in fp64 (no scrubbing by max / med3 / integer ReLU, no halo, padding lane or neighbouring frame
+    'masked' by a multiplication with 0), finite pixels within the full-size forward tolerances (fp16: the pruned B = 64 test's 1e-2), the clean
+    frames bit-identical to an all-clean batch (tests/test_emu_nonfinite.py, CPU tier).  (Through this network's 7 x 7 bottleneck a NaN pixel reaches
+    every output pixel at 224 x 224 as well: the masks are whole frames, in the reference too.)"""
+    from test_emu_nonfinite import check_nonfinite_forward, poisoned_batch, reference_forward
+    tol = {torch.float32: 1e-3, torch.float16: 1e-2, torch.bfloat16: 4e-2}[dtype]
+    models = inputs.product_models()
+    torch.manual_seed(41)
+    m = harness.randomize_bn(models.MobileNetSkipAdd((224, 224), pretrained=False, channels=models.PRUNED_CHANNELS if pruned else None), 42).eval()
+    x6, clean6, where6 = poisoned_batch(224, 224, rot=1 if pruned else 0, seed=7)
+    ref6 = reference_forward(m, x6)[:, 0]
+    for idx in ([0, 1, 2, 5], [3, 4, 5, 0]):
+        x, clean, where = x6[idx], clean6[idx], [where6[i] for i in idx]
+        p = harness.CPlan("hip", m, x.cuda(), keep=False, dtype=dtype)
+        y = p.forward(x.cuda())[:, 0].cpu()
+        y_clean = p.forward(clean.cuda())[:, 0].cpu()
+        p.close()
+        check_nonfinite_forward(y, y_clean, ref6[idx], where, tol)

@@ -460,3 +460,27 @@ def test_library_issued_rccl_exchange_two_ranks(tmp_path, bf16):
     assert torch.equal(r[0]["library"]["grad"], r[1]["library"]["grad"])
     for k in keys:
         assert torch.equal(r[0]["library"]["state"][k], r[1]["library"]["state"][k]), k
+
+
+_NAN_REF = {}
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_train_step_with_nan_pixel_batch32_like_reference(dtype):
+    """B = 32 at 224 x 224, default plan: one NaN pixel in frame 0.  As in the fp64 reference the batch statistics of every unit become NaN (every
+    statistics row column poisoned -- with workgroup counts that are multiples of 4), the loss is NaN, dLoss/dpred is torch's sign(NaN) = 0,
+    num_batches_tracked counts the step, and the same gradient tensors carry non-finite entries.  Then a clean step on the same plan, parameters
+    and running statistics restored, is bit for bit the clean step of a fresh plan (tests/test_emu_nonfinite.py, CPU tier)."""
+    from test_emu_nonfinite import TrainStep, check_clean_step_after_poison, check_nonfinite_train_step, reference_train_step
+    x, tgt = _batch(32, seed=5)
+    m = _model(seed=23).train()
+    xp = x.clone()
+    xp[0, :, 100, 37] = float("nan")
+    if "ref" not in _NAN_REF:
+        _NAN_REF["ref"] = reference_train_step(m, xp, tgt)
+    step = TrainStep("hip", m, xp.cuda(), dtype, 0)
+    got = step.run(xp.cuda(), tgt.cuda())
+    n_bad, n = check_nonfinite_train_step(got, _NAN_REF["ref"])
+    assert n == 114 and n_bad > 0
+    check_clean_step_after_poison("hip", m, x.cuda(), tgt.cuda(), dtype, 0, step)
+    step.close()
