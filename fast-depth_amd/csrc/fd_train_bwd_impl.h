@@ -32,26 +32,6 @@ int defer_weights(BwdCtx &c, const float *part, int nrows, int n, int KK, int C,
     return FD_OK;
 }
 
-// input rows per backward-data tile: balanced over the map (14 -> 7 + 7 instead of 8 + 6: both tiles full, smaller patches, one more workgroup per
-// CU); the upsampled modes produce 2 x 2 blocks per low-resolution pixel and need an even count
-inline int dw_dgrad_rows(const fd_train_plan *p, const TLayer &L)
-{
-    if (p->tune & FD_TUNE_DW_TH8) return 8;
-    // 3x3 stride-1 units: 14 rows where they divide the map (same reasoning as the forward kernel's larger tiles: fewer, fatter workgroups; the
-    // dz patch of 16 x 18 pixels = 41.5 KB stays below the 44.4 KB the paired weight-gradient role needs anyway)
-    // (measured, bf16 step: conv1 55.3 -> 52.1 us, conv3 59.2 -> 55.1, conv5 35.3 -> 32.7, 14x14 maps 20.5 -> 19.5)
-    if (L.d.ksize == 3 && L.d.stride == 1 && L.mode == 0 && L.in_h % 14 == 0) return 14;
-    const int th = ceil_div(L.in_h, ceil_div(L.in_h, L.d.ksize == 5 ? FD_T_DW5_DTH : (L.d.stride == 2 ? FD_T_S2_DTH : 8)));
-    return (L.mode != 0 || L.d.stride == 2) ? (th + 1) / 2 * 2 : th;     // (stride 2: the tile must hold whole receptive-field rows of its owned outputs)
-}
-inline int dw_dgrad_cols(const TLayer &L) { return L.d.ksize == 5 ? FD_T_DW5_DTW : (L.d.stride == 2 ? FD_T_S2_DTW : 16); }
-// Rows (columns) of the dz patch that an INPUT-space tile of t rows (columns, a multiple of the stride, starting on a multiple of it) reads: the
-// EXACT extent the kernel computes (fd_dw_dgrad_body: PH, PW) -- stride 1: t + K - 1; stride 2: t / 2 + 2.  (Rounds 1-2 requested up to 4 rows and
-// columns more: 58 KB instead of 38 for the 5x5 units = 2 resident workgroups per CU instead of 4.)
-inline int dw_dz_patch(int t, int k, int s) { return (t + k - 2) / s + (s == 2 ? 2 : 1); }
-inline size_t dw_bwd_lds(int ph, int pw, int cb, int k, int pstr, int le) { return lds_patch_bytes((long)ph * pw, pstr, le) + (size_t)k * k * cb * 4; }
-
-// (bwd_rows(plan, u, nblk), fd_train_plan.h: the statistics rows of unit u as the backward-data kernel of its consumer -- nblk workgroups per channel -- sees them)
 inline fd_bn_bwd_fin bwd_fin_args(BwdCtx &c, int i, size_t cf_off)
 {
     TLayer &L = c.p->layers[i];
@@ -64,54 +44,48 @@ int bn_bwd_finalize(BwdCtx &c, int i)
     FD_LAUNCH(fd_bn_bwd_finalize_rows_f32, dim3((unsigned)ceil_div(L.d.cout, 16)), dim3(256), 0, c.s, fa, L.d.cout);
     return check_launch("fd_bn_bwd_finalize_rows_f32");
 }
-// unit u's statistics rows are complete (its consumer's backward kernels have been launched): a capable first kernel of u finalises them itself
-// (TLayer::bwd_fin_rows, consumed when unit u is processed -- possibly by a later range call); otherwise the separate launch
-int finalize_or_defer(BwdCtx &c, int u)
+// unit u's statistics rows are complete (its consumer's backward kernels have been launched): unless u's first backward kernel finalises them itself
+// (TLayer::bwd_fin_rows), the separate launch
+int finalize_or_defer(BwdCtx &c, int u) { return c.p->layers[u].bwd_fin_rows ? FD_OK : bn_bwd_finalize(c, u); }
+// depthwise unit i's weight-gradient partial rows (one per row of its plan-sized region) go to the batched reduction
+int defer_dw_weights(BwdCtx &c, int i)
 {
-    TLayer &U = c.p->layers[u];
-    if (U.bwd_fin && U.nr_b <= (dw_bwd_row_kernel(c.p, u) ? FD_STAT_FIN_MAX_ROWS_ROWK : FD_STAT_FIN_MAX_ROWS_BLOCK)) { U.bwd_fin_rows = U.nr_b; return FD_OK; }     // (more rows: re-reading them in every workgroup costs more than the launch)
-    U.bwd_fin_rows = 0;
-    return bn_bwd_finalize(c, u);
+    const TLayer &L = c.p->layers[i];
+    const int kk = L.d.ksize * L.d.ksize;
+    return defer_weights(c, tws(c.p, L.wp_off), (int)(L.wp_elems / ((size_t)kk * L.d.cin)), kk * L.d.cin, kk, L.d.cin, c.grads[i].conv_weight);
 }
 
+// ---- depthwise backward, one launcher per form (TLayer::DwBwd, chosen and sized by fd_train_plan_create) ----
 template <typename T, int K, int S, int MODE, int ACT_IN, int ADD_SG>
-int launch_dw_dgrad(BwdCtx &c, int i, int *nblk_out)
+int launch_dw_dgrad(BwdCtx &c, int i)
 {
     TLayer &L = c.p->layers[i];
     TLayer &P = c.p->layers[L.d.src];
-    const int cb = L.dw_n << L.cbq, le = L.dw_n == 8 ? 2 : 4;
-    L.lds_rounding = (L.lds_rounding & ~2) | (L.dw_n == 8 ? 2 : 0);
-    L.bwd_rows = 0;
-    const int TH = dw_dgrad_rows(c.p, L), TW = dw_dgrad_cols(L);
-    const int tiles_x = ceil_div(L.in_w, TW), tiles_y = ceil_div(L.in_h, TH);
-    const int ph = dw_dz_patch(TH, K, S), pw = dw_dz_patch(TW, K, S);
-    const size_t lds = dw_bwd_lds(ph, pw, cb, K, L.bpstr, le);
-    dim3 grid(tiles_x * tiles_y, ceil_div(L.d.cin, cb), c.p->B);
     const TLayer *Kp = L.d.skip >= 0 ? &c.p->layers[L.d.skip] : nullptr;
+    const dim3 grid(L.d_gx, ceil_div(L.d.cin, L.dw_n << L.cbq), c.p->B);
     fd_by_lane_width<T>(L.dw_n, [&](auto nt) {
         constexpr int NL = decltype(nt)::value;
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)fd_dw_dgrad<T, K, S, MODE, ACT_IN, ADD_SG, NL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        FD_LAUNCH((fd_dw_dgrad<T, K, S, MODE, ACT_IN, ADD_SG, NL>), grid, dim3(256), lds, c.s, twt<T>(c.p, L.g_off), twt<T>(c.p, L.z_off), tws(c.p, L.coef_off),
+        if (L.blds2 > 64 * 1024) (void)hipFuncSetAttribute((const void *)fd_dw_dgrad<T, K, S, MODE, ACT_IN, ADD_SG, NL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.blds2);
+        FD_LAUNCH((fd_dw_dgrad<T, K, S, MODE, ACT_IN, ADD_SG, NL>), grid, dim3(256), L.blds2, c.s, twt<T>(c.p, L.g_off), twt<T>(c.p, L.z_off), tws(c.p, L.coef_off),
                   c.params[i].conv_weight, twt<T>(c.p, P.z_off), tws(c.p, P.st_off), ADD_SG ? twt<T>(c.p, P.sg_off) : (const T *)nullptr,
-                  twt<T>(c.p, P.g_off), Kp ? twt<T>(c.p, Kp->sg_off) : (T *)nullptr, bwd_rows(c.p, L.d.src, (long)tiles_x * tiles_y * c.p->B),
-                  L.in_h, L.in_w, L.out_h, L.out_w, L.d.cin, L.cbq, TH, TW, tiles_x, L.csplit, L.bpstr);
+                  twt<T>(c.p, P.g_off), Kp ? twt<T>(c.p, Kp->sg_off) : (T *)nullptr, bwd_rows(c.p, L.d.src),
+                  L.in_h, L.in_w, L.out_h, L.out_w, L.d.cin, L.cbq, L.d_th, L.d_tw, L.d_tiles_x, L.csplit, L.bpstr);
     });
-    *nblk_out = tiles_x * tiles_y * c.p->B;
     return check_launch("fd_dw_dgrad");
 }
 
 template <typename T, int ACT_IN, int ADD_SG>
-int dispatch_dw_dgrad(BwdCtx &c, int i, int *nblk)
+int dispatch_dw_dgrad(BwdCtx &c, int i)
 {
     const TLayer &L = c.p->layers[i];
     const int key = L.d.ksize * 100 + L.d.stride * 10 + L.mode;
     switch (key) {
-    case 310: return launch_dw_dgrad<T, 3, 1, 0, ACT_IN, ADD_SG>(c, i, nblk);
-    case 320: return launch_dw_dgrad<T, 3, 2, 0, ACT_IN, ADD_SG>(c, i, nblk);
-    case 510: return launch_dw_dgrad<T, 5, 1, 0, ACT_IN, ADD_SG>(c, i, nblk);
-    case 511: return launch_dw_dgrad<T, 5, 1, 1, ACT_IN, ADD_SG>(c, i, nblk);
-    case 512: return launch_dw_dgrad<T, 5, 1, 2, ACT_IN, ADD_SG>(c, i, nblk);
-    case 513: return launch_dw_dgrad<T, 5, 1, 3, ACT_IN, ADD_SG>(c, i, nblk);
+    case 310: return launch_dw_dgrad<T, 3, 1, 0, ACT_IN, ADD_SG>(c, i);
+    case 320: return launch_dw_dgrad<T, 3, 2, 0, ACT_IN, ADD_SG>(c, i);
+    case 510: return launch_dw_dgrad<T, 5, 1, 0, ACT_IN, ADD_SG>(c, i);
+    case 511: return launch_dw_dgrad<T, 5, 1, 1, ACT_IN, ADD_SG>(c, i);
+    case 512: return launch_dw_dgrad<T, 5, 1, 2, ACT_IN, ADD_SG>(c, i);
+    case 513: return launch_dw_dgrad<T, 5, 1, 3, ACT_IN, ADD_SG>(c, i);
     }
     return fail(FD_ERR_INVALID, "train: depthwise backward k=%d stride=%d mode=%d has no kernel", L.d.ksize, L.d.stride, L.mode);
 }
@@ -123,28 +97,15 @@ int launch_dw_wgrad_acts(BwdCtx &c, int i)
     TLayer &P = c.p->layers[L.d.src];
     const TLayer *Kp = L.d.skip >= 0 ? &c.p->layers[L.d.skip] : nullptr;
     const int key = L.d.ksize * 100 + L.d.stride * 10 + L.mode;
-    float *wpart = tws(c.p, L.wp_off);
-    // tiles per workgroup (along x): as many as keep >= ~1536 workgroups in flight
-    const int ncb_w = ceil_div(L.d.cin, L.dw_n << L.cbq);
-    const int btx = ceil_div(L.out_w, L.btw), bty = ceil_div(L.out_h, L.bth);     // the backward-weights kernel's own output tiles (the forward's may be larger)
-    int tpw = std::max(1, std::min(btx, (int)((long)btx * bty * ncb_w * c.p->B / FD_DW_WGRAD_TARGET_WGS)));
-    if (c.p->tune & FD_TUNE_WGRAD_TILE_ROWS) tpw = btx;
-    const int groups_x = ceil_div(btx, tpw);
-    tpw = ceil_div(btx, groups_x);
-    const dim3 wgrid(groups_x * bty, ncb_w, c.p->B);
-    // LDS: activated input patch + dz tile, both [pixels][cb + 4] floats; the final reduction (npt/K groups x K*K taps x cb) reuses it
-    const int cbw = L.dw_n << L.cbq, le = L.dw_n == 8 ? 2 : 4, th_in = (L.bth - 1) * L.d.stride + L.d.ksize, tw_in = (L.btw - 1) * L.d.stride + L.d.ksize;
-    const size_t wlds = std::max(lds_patch_bytes((long)th_in * tw_in + L.bth * L.btw, L.bpstr, le), (size_t)((256 >> L.cbq) / L.d.ksize) * L.d.ksize * L.d.ksize * cbw * 4);
-    if (wlds > 64 * 1024) return fail(FD_ERR_INVALID, "depthwise wgrad: LDS request %zu exceeds 64 KiB", wlds);
-    const int wblk = groups_x * bty * c.p->B;
+    const dim3 wgrid(L.w_gx, ceil_div(L.d.cin, L.dw_n << L.cbq), c.p->B);
 #define FD_DWW(K_, S_, M_)                                                                                                         \
     case K_ * 100 + S_ * 10 + M_:                                                                                                  \
         fd_by_lane_width<T>(L.dw_n, [&](auto nt) {                                                                                \
             constexpr int NL = decltype(nt)::value;                                                                               \
-            FD_LAUNCH((fd_dw_wgrad<T, K_, S_, M_, ACT1, ACT2, NL>), wgrid, dim3(256), wlds, c.s, twt<T>(c.p, P.z_off), tws(c.p, P.st_off),  \
+            FD_LAUNCH((fd_dw_wgrad<T, K_, S_, M_, ACT1, ACT2, NL>), wgrid, dim3(256), L.blds, c.s, twt<T>(c.p, P.z_off), tws(c.p, P.st_off),  \
                       Kp ? twt<T>(c.p, Kp->z_off) : (const T *)nullptr, Kp ? tws(c.p, Kp->st_off) : (const float *)nullptr,           \
-                      twt<T>(c.p, L.g_off), twt<T>(c.p, L.z_off), tws(c.p, L.coef_off), wpart, L.in_h, L.in_w, L.out_h, L.out_w, L.d.cin,     \
-                      L.cbq, L.bth, L.btw, btx, tpw, L.csplit, L.bpstr);                                                          \
+                      twt<T>(c.p, L.g_off), twt<T>(c.p, L.z_off), tws(c.p, L.coef_off), tws(c.p, L.wp_off), L.in_h, L.in_w, L.out_h, L.out_w, L.d.cin, \
+                      L.cbq, L.bth, L.btw, L.w_tiles_x, L.w_tpw, L.csplit, L.bpstr);                                              \
         });                                                                                                                        \
         break;
     switch (key) {
@@ -152,246 +113,140 @@ int launch_dw_wgrad_acts(BwdCtx &c, int i)
     default: return fail(FD_ERR_INVALID, "train: depthwise wgrad has no kernel for this layer");
     }
 #undef FD_DWW
-    int rc = check_launch("fd_dw_wgrad");
-    if (rc) return rc;
-    const int kk = L.d.ksize * L.d.ksize;
-    if ((size_t)wblk * kk * L.d.cin > L.wp_elems) return fail(FD_ERR_STATE, "depthwise weight-gradient partial region too small");
-    return defer_weights(c, wpart, wblk, kk * L.d.cin, kk, L.d.cin, c.grads[i].conv_weight);
+    return check_launch("fd_dw_wgrad");
 }
 
+// SEPARATE: the two kernels one after the other (every activation / composition has an instance)
 template <typename T>
-int launch_dw_wgrad(BwdCtx &c, int i)
+int launch_dw_separate(BwdCtx &c, int i)
 {
     const TLayer &L = c.p->layers[i];
-    const int a1 = c.p->layers[L.d.src].d.act, a2 = L.d.skip >= 0 ? c.p->layers[L.d.skip].d.act : FD_ACT_RELU6;
-    if (a1 == FD_ACT_RELU6 && a2 == FD_ACT_RELU6) return launch_dw_wgrad_acts<T, FD_ACT_RELU6_, FD_ACT_RELU6_>(c, i);
-    if (a1 == FD_ACT_RELU && a2 == FD_ACT_RELU6) return launch_dw_wgrad_acts<T, FD_ACT_RELU_, FD_ACT_RELU6_>(c, i);
-    if (a1 == FD_ACT_RELU && a2 == FD_ACT_RELU) return launch_dw_wgrad_acts<T, FD_ACT_RELU_, FD_ACT_RELU_>(c, i);
-    return launch_dw_wgrad_acts<T, FD_ACT_RELU6_, FD_ACT_RELU_>(c, i);
+    const TLayer &P = c.p->layers[L.d.src];
+    const int a1 = P.d.act, a2 = L.d.skip >= 0 ? c.p->layers[L.d.skip].d.act : FD_ACT_RELU6;
+    int rc;
+    if (a1 == FD_ACT_RELU6 && a2 == FD_ACT_RELU6) rc = launch_dw_wgrad_acts<T, FD_ACT_RELU6_, FD_ACT_RELU6_>(c, i);
+    else if (a1 == FD_ACT_RELU && a2 == FD_ACT_RELU6) rc = launch_dw_wgrad_acts<T, FD_ACT_RELU_, FD_ACT_RELU6_>(c, i);
+    else if (a1 == FD_ACT_RELU && a2 == FD_ACT_RELU) rc = launch_dw_wgrad_acts<T, FD_ACT_RELU_, FD_ACT_RELU_>(c, i);
+    else rc = launch_dw_wgrad_acts<T, FD_ACT_RELU6_, FD_ACT_RELU_>(c, i);
+    if (rc || (rc = defer_dw_weights(c, i))) return rc;
+    const bool add = P.skip_consumer >= 0 && L.mode == 0;
+    if (a1 == FD_ACT_RELU6) return add ? dispatch_dw_dgrad<T, FD_ACT_RELU6_, 1>(c, i) : dispatch_dw_dgrad<T, FD_ACT_RELU6_, 0>(c, i);
+    return add ? dispatch_dw_dgrad<T, FD_ACT_RELU_, 1>(c, i) : dispatch_dw_dgrad<T, FD_ACT_RELU_, 0>(c, i);
 }
 
-// Both backward kernels of a depthwise unit in ONE launch (fd_dw_bwd); returns FD_OK with *paired = false when this unit's combination of
-// kernel size / stride / input composition / activations has no paired instance (the caller then launches the two kernels one after the other).
-#ifndef FD_DW3_ROWS_SMALL_BAND
-#define FD_DW3_ROWS_SMALL_BAND 7
-#endif
-template <typename T, int K, int S, int MODE, int ACT1, int ACT2, int ADD_SG>
-int launch_dw_bwd_pair(BwdCtx &c, int i, int *nblk_out)
+// the operands of unit i's backward and the LDS-tiled geometry (fd_dw_bwd_args: every other form copies its operands from here)
+template <typename T, int ADD_SG>
+fd_dw_bwd_args<T> dw_bwd_args(BwdCtx &c, int i)
 {
-    TLayer &L = c.p->layers[i];
-    TLayer &P = c.p->layers[L.d.src];
+    const TLayer &L = c.p->layers[i];
+    const TLayer &P = c.p->layers[L.d.src];
     const TLayer *Kp = L.d.skip >= 0 ? &c.p->layers[L.d.skip] : nullptr;
-    const int cb = L.dw_n << L.cbq, le = L.dw_n == 8 ? 2 : 4;
-    L.lds_rounding = (L.lds_rounding & ~2) | (L.dw_n == 8 ? 2 : 0);
     fd_dw_bwd_args<T> a{};
     a.G = twt<T>(c.p, L.g_off); a.Z = twt<T>(c.p, L.z_off); a.Zin = twt<T>(c.p, P.z_off);
     a.Zskip = Kp ? twt<T>(c.p, Kp->z_off) : nullptr; a.SG = ADD_SG ? twt<T>(c.p, P.sg_off) : nullptr;
     a.Gin = twt<T>(c.p, P.g_off); a.SGout = Kp ? twt<T>(c.p, Kp->sg_off) : nullptr;
     a.coef = tws(c.p, L.coef_off); a.w = c.params[i].conv_weight; a.st_in = tws(c.p, P.st_off); a.st_skip = Kp ? tws(c.p, Kp->st_off) : nullptr;
+    a.sr = bwd_rows(c.p, L.d.src);
     a.wpart = tws(c.p, L.wp_off);
     a.Hin = L.in_h; a.Win = L.in_w; a.Ho = L.out_h; a.Wo = L.out_w; a.C = L.d.cin; a.cbq = L.cbq; a.csplit = L.csplit; a.pstr = L.bpstr; a.B = c.p->B;
-    // backward-data geometry (launch_dw_dgrad)
-    a.d_th = dw_dgrad_rows(c.p, L); a.d_tw = dw_dgrad_cols(L);
-    a.d_tiles_x = ceil_div(L.in_w, a.d_tw);
-    a.d_gx = a.d_tiles_x * ceil_div(L.in_h, a.d_th); a.d_gy = ceil_div(L.d.cin, cb);
-    const int ph = dw_dz_patch(a.d_th, K, S), pw = dw_dz_patch(a.d_tw, K, S);
-    const size_t lds_d = dw_bwd_lds(ph, pw, cb, K, L.bpstr, le);
-    // backward-weights geometry (launch_dw_wgrad_acts); the pair keeps roughly the same number of workgroups in flight per role
-    const int btx = ceil_div(L.out_w, L.btw), bty = ceil_div(L.out_h, L.bth);
-    int tpw = std::max(1, std::min(btx, (int)((long)btx * bty * ceil_div(L.d.cin, cb) * c.p->B / FD_DW_WGRAD_TARGET_WGS)));
-    if (c.p->tune & FD_TUNE_WGRAD_TILE_ROWS) tpw = btx;
-    const int groups_x = ceil_div(btx, tpw);
-    tpw = ceil_div(btx, groups_x);
-    a.w_th = L.bth; a.w_tw = L.btw; a.w_tiles_x = btx; a.w_tpw = tpw; a.w_gx = groups_x * bty; a.w_gy = ceil_div(L.d.cin, cb);
-    const int th_in = (L.bth - 1) * S + K, tw_in = (L.btw - 1) * S + K;
-    const size_t lds_w = std::max(lds_patch_bytes((long)th_in * tw_in + L.bth * L.btw, L.bpstr, le), (size_t)((256 >> L.cbq) / K) * K * K * cb * 4);
-    size_t lds = align_up(std::max(lds_d, lds_w), 16);
-    if (L.bwd_fin_rows) lds += (size_t)4 * cb * 4;          // + the coefficient block of the in-kernel finalisation (fd_bn_bwd_fin::cf_off)
-    if (lds > 160 * 1024) return fail(FD_ERR_INVALID, "depthwise backward pair: LDS request %zu exceeds 160 KiB", lds);
-    const int kk = K * K;
-    // 16-bit plans, 5x5 on up2 + skip (decode_conv3 / 4 / 5 .0): both gradients on the row-walking pixel-pair kernel (fd_kernels_dw5p_bwd.h) -- one launch,
-    // backward-data workgroups first, then the weight-gradient workgroups of the same image (same XCD: the second role finds G / z in its L2)
-    if constexpr (K == 5 && S == 1 && MODE == 2 && ADD_SG == 0 && !std::is_same<T, float>::value) {
-        if (L.in_w % 4 == 0 && L.in_h % 2 == 0 && L.d.cin % 8 == 0 && (double)L.in_h * L.in_w * L.d.cin * 2.0 < 2147483648.0 &&
-            !(c.p->tune & (FD_TUNE_NO_DW5_ROWS | FD_TUNE_DW_BWD1 | FD_TUNE_DW_BWD_PAIR))) {
-            fd_dw5_bwd_args<T> b{};
-            b.G = a.G; b.Z = a.Z; b.Zin = a.Zin; b.Zskip = a.Zskip; b.Gin = a.Gin; b.SGout = a.SGout;
-            b.coef = a.coef; b.w = a.w; b.st_in = a.st_in; b.st_skip = a.st_skip; b.wpart = a.wpart;
-            b.H = L.in_h; b.W = L.in_w; b.C = L.d.cin; b.groups_x = ceil_div(L.in_w, 8);
-            const int bands = std::max(1, (L.in_h + 7) / 14);
-            b.bh_d = b.bh_w = ceil_div(ceil_div(L.in_h, bands), 2) * 2;
-            b.wgs_d = b.wgs_w = ceil_div((long)b.groups_x * ceil_div(L.in_h, b.bh_d), 4);
-            b.sr = bwd_rows(c.p, L.d.src, (long)b.wgs_d * c.p->B);
-            if (L.bwd_fin_rows) b.fin = bwd_fin_args(c, i, 0);
-            const int wrows = b.wgs_w * c.p->B;
-            if ((size_t)wrows * kk * L.d.cin > L.wp_elems) return fail(FD_ERR_STATE, "depthwise weight-gradient partial region too small");
-            L.lds_rounding = (L.lds_rounding & ~(2 | 8)) | 2 | 8;       // dz and the re-created input rounded to the storage type; the backward-data taps too
-            L.bwd_rows = 1;
-            FD_LAUNCH((fd_dw5_bwd_rows<T, ACT1, ACT2>), dim3((unsigned)(b.wgs_d + b.wgs_w), (unsigned)ceil_div(L.d.cin, 64), (unsigned)c.p->B), dim3(256), 0, c.s, b);
-            int rc5 = check_launch("fd_dw5_bwd_rows");
-            if (rc5) return rc5;
-            *nblk_out = b.wgs_d * c.p->B;
-            return defer_weights(c, b.wpart, wrows, kk * L.d.cin, kk, L.d.cin, c.grads[i].conv_weight);
+    a.d_th = L.d_th; a.d_tw = L.d_tw; a.d_tiles_x = L.d_tiles_x; a.d_gx = L.d_gx; a.d_gy = ceil_div(L.d.cin, L.dw_n << L.cbq);
+    a.w_th = L.bth; a.w_tw = L.btw; a.w_tiles_x = L.w_tiles_x; a.w_tpw = L.w_tpw; a.w_gx = L.w_gx; a.w_gy = a.d_gy;
+    if (L.bwd_fin_rows && (L.bwd == TLayer::DwBwd::BWD1 || L.bwd == TLayer::DwBwd::PAIR))
+        a.fin = bwd_fin_args(c, i, L.blds - (size_t)4 * (L.dw_n << L.cbq) * 4);       // (the coefficient block ends their LDS)
+    return a;
+}
+
+// the forms with a kernel instance per (kernel size, stride, input composition, activations): fd_by_dw_instance
+template <typename T, int K, int S, int MODE, int ACT1, int ACT2, int ADD_SG>
+int launch_dw_form(BwdCtx &c, int i)
+{
+    using F = TLayer::DwBwd;
+    constexpr bool H16 = !std::is_same<T, float>::value;
+    const TLayer &L = c.p->layers[i];
+    const fd_dw_bwd_args<T> a = dw_bwd_args<T, ADD_SG>(c, i);
+    const unsigned B = (unsigned)c.p->B;
+    switch (L.bwd) {
+    case F::ROWS5:                                            // dz and the re-created input rounded to the storage type; the backward-data taps too
+        if constexpr (H16 && K == 5 && S == 1 && MODE == 2 && !ADD_SG) {
+            const fd_dw5_bwd_args<T> b{a.G, a.Z, a.Zin, a.Zskip, a.Gin, a.SGout, a.coef, a.w, a.st_in, a.st_skip, a.sr, a.wpart,
+                                       L.in_h, L.in_w, L.d.cin, L.rb_groups, L.rb_bh, L.rb_bh, L.rb_wgs, L.rb_wgs, L.bwd_fin_rows ? bwd_fin_args(c, i, 0) : fd_bn_bwd_fin{}};
+            FD_LAUNCH((fd_dw5_bwd_rows<T, ACT1, ACT2>), dim3((unsigned)(2 * L.rb_wgs), (unsigned)ceil_div(L.d.cin, 64), B), dim3(256), 0, c.s, b);
+            return check_launch("fd_dw5_bwd_rows");
         }
-    }
-    L.lds_rounding &= ~8;
-    // 16-bit plans, 3x3 stride 1 on plain inputs (conv1.0 / conv3.0 / conv5.0 / the 14x14 units ...): both gradients on the row-walking fp32-window kernel
-    // (fd_kernels_dw5p_bwd.h: fd_dw3_bwd_rows); nothing is rounded there, so the unit reports no LDS rounding
-    if constexpr (K == 3 && S == 1 && MODE == 0 && ADD_SG == 0 && !std::is_same<T, float>::value) {
-        if (L.d.cin % 8 == 0 && (double)L.in_h * L.in_w * L.d.cin * 2.0 < 2147483648.0 && (long)L.in_h * L.in_w >= FD_DW3_ROWS_MIN_PIXELS &&
-            !(c.p->tune & (FD_TUNE_NO_DW5_ROWS | FD_TUNE_DW_BWD1 | FD_TUNE_DW_BWD_PAIR | FD_TUNE_FORCE_DW_H8))) {
-            fd_dw3_bwd_args<T> b{};
-            b.G = a.G; b.Z = a.Z; b.Zin = a.Zin; b.Gin = a.Gin; b.coef = a.coef; b.w = a.w; b.st_in = a.st_in; b.wpart = a.wpart;
-            const int cl = L.d.cin <= 32 ? 16 : 32;          // channel lanes per strip: a 32-channel unit (conv1.0) would leave half of every wave idle at 32
-            b.H = L.in_h; b.W = L.in_w; b.C = L.d.cin; b.groups_x = ceil_div(L.in_w, 4 * (64 / cl));
-            // bands of ~14 rows on the large maps; the 14x14 / 7x7 maps take bands of 7 (twice the waves: their launches are latency-, not issue-bound)
-            const int bands = L.in_h <= 7 ? ceil_div(L.in_h, 4) : L.in_h <= 14 ? ceil_div(L.in_h, FD_DW3_ROWS_SMALL_BAND) : std::max(1, (L.in_h + 7) / 14);     // (7x7: 512 -> 1024 waves, -2.7 us)
-            b.bh_d = b.bh_w = ceil_div(L.in_h, bands);
-            b.wgs_d = b.wgs_w = ceil_div((long)b.groups_x * ceil_div(L.in_h, b.bh_d), 4);
-            b.sr = bwd_rows(c.p, L.d.src, (long)b.wgs_d * c.p->B);
-            if (L.bwd_fin_rows) b.fin = bwd_fin_args(c, i, 0);
-            const int wrows = b.wgs_w * c.p->B;
-            if ((size_t)wrows * kk * L.d.cin > L.wp_elems) return fail(FD_ERR_STATE, "depthwise weight-gradient partial region too small");
-            L.lds_rounding &= ~2;
-            L.bwd_rows = 1;
-            const dim3 g3((unsigned)(b.wgs_d + b.wgs_w), (unsigned)ceil_div(L.d.cin, 2 * cl), (unsigned)c.p->B);
-            if (cl == 16) FD_LAUNCH((fd_dw3_bwd_rows<T, ACT1, 16>), g3, dim3(256), 0, c.s, b);
+        break;
+    case F::ROWS3:                                            // (nothing rounded)
+        if constexpr (H16 && K == 3 && S == 1 && MODE == 0 && !ADD_SG) {
+            const fd_dw3_bwd_args<T> b{a.G, a.Z, a.Zin, a.Gin, a.coef, a.w, a.st_in, a.sr, a.wpart, L.in_h, L.in_w, L.d.cin, L.rb_groups, L.rb_bh, L.rb_bh, L.rb_wgs, L.rb_wgs,
+                                       L.bwd_fin_rows ? bwd_fin_args(c, i, 0) : fd_bn_bwd_fin{}};
+            const dim3 g3((unsigned)(2 * L.rb_wgs), (unsigned)ceil_div(L.d.cin, 2 * L.rb_cl), B);
+            if (L.rb_cl == 16) FD_LAUNCH((fd_dw3_bwd_rows<T, ACT1, 16>), g3, dim3(256), 0, c.s, b);
             else FD_LAUNCH((fd_dw3_bwd_rows<T, ACT1, 32>), g3, dim3(256), 0, c.s, b);
-            int rc3 = check_launch("fd_dw3_bwd_rows");
-            if (rc3) return rc3;
-            *nblk_out = b.wgs_d * c.p->B;
-            return defer_weights(c, b.wpart, wrows, kk * L.d.cin, kk, L.d.cin, c.grads[i].conv_weight);
+            return check_launch("fd_dw3_bwd_rows");
         }
-    }
-    // 16-bit plans, 3x3 stride 2 (conv2.0 / conv4.0 / conv6.0 / conv12.0): ONE row-walking kernel produces both gradients from one pass over z_in, G, z and the
-    // skip gradient (fd_kernels_dw5p_bwd.h: fd_dw3s2_bwd_rows); these units are byte-bound and the paired forms read their operands twice
-    if constexpr (K == 3 && S == 2 && MODE == 0 && !std::is_same<T, float>::value) {
-        if (L.d.cin % 8 == 0 && (double)L.in_h * L.in_w * L.d.cin * 2.0 < 2147483648.0 &&
-            !(c.p->tune & (FD_TUNE_NO_DW5_ROWS | FD_TUNE_DW_BWD1 | FD_TUNE_DW_BWD_PAIR | FD_TUNE_FORCE_DW_H8 | FD_TUNE_DW_FORCE_ROWS | FD_TUNE_DW_NO_ROWS))) {
-            fd_dw3s2_bwd_args<T> b{};
-            b.G = a.G; b.Z = a.Z; b.Zin = a.Zin; b.SG = a.SG; b.Gin = a.Gin; b.coef = a.coef; b.w = a.w; b.st_in = a.st_in; b.wpart = a.wpart;
-            b.Ho = L.out_h; b.Wo = L.out_w; b.C = L.d.cin; b.groups_x = ceil_div(L.out_w, 8);
-            const int bands = L.out_h <= 7 ? ceil_div(L.out_h, 2) : L.out_h <= 14 ? ceil_div(L.out_h, 4) : std::max(1, (L.out_h + 3) / 7);     // ~7 output rows (14 input rows) per band; the small maps take 4 / 2
-            b.bh = ceil_div(L.out_h, bands);
-            b.wgs = ceil_div((long)b.groups_x * ceil_div(L.out_h, b.bh), 4);
-            b.sr = bwd_rows(c.p, L.d.src, (long)b.wgs * c.p->B);
-            if (L.bwd_fin_rows) b.fin = bwd_fin_args(c, i, 0);
-            const int wrows = b.wgs * c.p->B;
-            if ((size_t)wrows * kk * L.d.cin > L.wp_elems) return fail(FD_ERR_STATE, "depthwise weight-gradient partial region too small");
-            L.lds_rounding &= ~2;
-            L.bwd_rows = 1;
-            FD_LAUNCH((fd_dw3s2_bwd_rows<T, ACT1, ADD_SG>), dim3((unsigned)b.wgs, (unsigned)ceil_div(L.d.cin, 64), (unsigned)c.p->B), dim3(256), 0, c.s, b);
-            int rc2 = check_launch("fd_dw3s2_bwd_rows");
-            if (rc2) return rc2;
-            *nblk_out = b.wgs * c.p->B;
-            return defer_weights(c, b.wpart, wrows, kk * L.d.cin, kk, L.d.cin, c.grads[i].conv_weight);
+        break;
+    case F::ROWS3S2:
+        if constexpr (H16 && K == 3 && S == 2 && MODE == 0) {
+            const fd_dw3s2_bwd_args<T> b{a.G, a.Z, a.Zin, a.SG, a.Gin, a.coef, a.w, a.st_in, a.sr, a.wpart, L.out_h, L.out_w, L.d.cin, L.rb_groups, L.rb_bh, L.rb_wgs,
+                                         L.bwd_fin_rows ? bwd_fin_args(c, i, 0) : fd_bn_bwd_fin{}};
+            FD_LAUNCH((fd_dw3s2_bwd_rows<T, ACT1, ADD_SG>), dim3((unsigned)L.rb_wgs, (unsigned)ceil_div(L.d.cin, 64), B), dim3(256), 0, c.s, b);
+            return check_launch("fd_dw3s2_bwd_rows");
         }
-    }
-    // The stride-2 3x3 units of the large maps (channel-group count a power of two in 8 ... 64): two register-window kernels without LDS staging
-    // (fd_dw3s2_dgrad_rows over input columns, fd_dw3_wgrad_rows over output columns), row strips as high as still leave >= ~1024 workgroups
-    {
-        const int cgn = L.d.cin / 4;
-        // measured (us, rows pair vs single-staging kernel): bf16 conv2.0 48.9 + 16.8 vs 79.3, conv4.0 33.4 + 11.0 vs 48.2, conv6.0 (14x14 outputs) 23.4 + 7.8 vs 29.6;
-        // fp32 conv2.0 69.0 + 26.7 vs 96.2, conv4.0 40.7 + 15.3 vs 55.2 (equal: both forms move the fp32 bytes at the same rate) -> 16-bit plans, maps >= 28x28
-        if (dw_bwd_on_rows(c.p, L)) {
-            L.lds_rounding &= ~2;
-            const int gxd = ceil_div((long)L.in_w * cgn, 256), h2 = L.in_h / 2;
-            int th2 = h2;
-            while (th2 > 2 && (long)gxd * ceil_div(h2, th2) * c.p->B < 1024) th2 = (th2 + 1) / 2;
-            const int gyd = ceil_div(h2, th2);
-            a.sr = bwd_rows(c.p, L.d.src, (long)gxd * gyd * c.p->B);
-            FD_LAUNCH((fd_dw3s2_dgrad_rows<T, ACT1, ADD_SG>), dim3(gxd, gyd, c.p->B), dim3(256), 0, c.s, a.G, a.Z, a.coef, a.w, a.Zin, a.st_in, a.SG, a.Gin, a.sr,
-                      L.in_h, L.in_w, L.out_h, L.out_w, L.d.cin, th2);
-            int rcr = check_launch("fd_dw3s2_dgrad_rows");
-            if (rcr) return rcr;
-            const int gxw = ceil_div((long)L.out_w * cgn, 256);
-            int thw = L.out_h;
-            while (thw > 4 && (long)gxw * ceil_div(L.out_h, thw) * c.p->B < 1024) thw = (thw + 1) / 2;
-            const int gyw = ceil_div(L.out_h, thw), wrows = gxw * gyw * c.p->B;
-            if ((size_t)wrows * kk * L.d.cin > L.wp_elems) return fail(FD_ERR_STATE, "depthwise weight-gradient partial region too small");
-            FD_LAUNCH((fd_dw3_wgrad_rows<T, 2, ACT1>), dim3(gxw, gyw, c.p->B), dim3(256), 0, c.s, a.Zin, a.st_in, a.G, a.Z, a.coef, a.wpart,
-                      L.in_h, L.in_w, L.out_h, L.out_w, L.d.cin, thw);
-            if ((rcr = check_launch("fd_dw3_wgrad_rows"))) return rcr;
-            *nblk_out = gxd * gyd * c.p->B;
-            return defer_weights(c, a.wpart, wrows, kk * L.d.cin, kk, L.d.cin, c.grads[i].conv_weight);
+        break;
+    case F::REGWIN_S2:
+        if constexpr (K == 3 && S == 2 && MODE == 0) {
+            FD_LAUNCH((fd_dw3s2_dgrad_rows<T, ACT1, ADD_SG>), L.rw_grid_d, dim3(256), 0, c.s, a.G, a.Z, a.coef, a.w, a.Zin, a.st_in, a.SG, a.Gin, a.sr,
+                      L.in_h, L.in_w, L.out_h, L.out_w, L.d.cin, L.rw_th_d);
+            const int rc = check_launch("fd_dw3s2_dgrad_rows");
+            if (rc) return rc;
+            FD_LAUNCH((fd_dw3_wgrad_rows<T, 2, ACT1>), L.rw_grid_w, dim3(256), 0, c.s, a.Zin, a.st_in, a.G, a.Z, a.coef, a.wpart, L.in_h, L.in_w, L.out_h, L.out_w, L.d.cin, L.rw_th_w);
+            return check_launch("fd_dw3_wgrad_rows");
         }
-    }
-    // (stride-1 3x3 units: the LDS-tiled backward-data kernel on its own + fd_dw3_wgrad_rows instead of the paired launch measured equal -- conv1.0
-    // 31.2 + 20.3 vs 52.8 us, conv3.0 34.8 + 20.5 vs 56.4, conv5.0 22.1 + 14.6 vs 33.1 -- the pair stays)
-    // measured (bf16, batch 32): the single-staging kernel wins on the stride-2 units (conv2.0 84 vs 103 us, conv4.0 50 vs 57, conv6.0 31 vs 35) and
-    // loses on the stride-1 3x3 ones (conv1.0 68 vs 57, 14x14 maps 22.4 vs 19.5: two tap phases back to back in one workgroup at lower residency);
-    // the 5x5 units tie.  FD_TUNE_DW_BWD1 forces it everywhere (tests), FD_TUNE_DW_BWD_PAIR nowhere.
-    if (!(c.p->tune & FD_TUNE_DW_BWD_PAIR) && (S == 2 || (c.p->tune & FD_TUNE_DW_BWD1))) {
-        // ONE workgroup per input-space tile stages the dz patch and the forward-input patch once and produces both gradients (fd_dw_bwd1)
-        const int oth = a.d_th / S, otw = a.d_tw / S;
-        const int th_in1 = (oth - 1) * S + K, tw_in1 = (otw - 1) * S + K;
-        const int ph1 = (a.d_th + K - 2) / S + 2, pw1 = (a.d_tw + K - 2) / S + 2;          // upper bound of the dz patch
-        size_t lds1 = align_up(std::max(lds_patch_bytes((long)ph1 * pw1 + th_in1 * tw_in1, L.bpstr, le) + (size_t)kk * cb * 4, (size_t)((256 >> L.cbq) / K) * kk * cb * 4 + 8192), 16);
-        if (L.bwd_fin_rows) { a.fin = bwd_fin_args(c, i, lds1); lds1 += (size_t)4 * cb * 4; }
-        if (lds1 > 160 * 1024) return fail(FD_ERR_INVALID, "depthwise backward: LDS request %zu exceeds 160 KiB", lds1);
-        const int wblk1 = a.d_gx * c.p->B;
-        if ((size_t)wblk1 * kk * L.d.cin > L.wp_elems) return fail(FD_ERR_STATE, "depthwise weight-gradient partial region too small");
-        a.sr = bwd_rows(c.p, L.d.src, wblk1);
+        break;
+    case F::BWD1:                                             // (the instance with the in-kernel finalisation costs registers: only where it replaces a launch)
         fd_by_lane_width<T>(L.dw_n, [&](auto nt) {
             constexpr int NL = decltype(nt)::value;
-            if (a.fin.rows) {                                 // (the instance with the in-kernel finalisation costs registers: only where it replaces a launch)
-                (void)hipFuncSetAttribute((const void *)fd_dw_bwd1<T, K, S, MODE, ACT1, ACT2, ADD_SG, NL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-                FD_LAUNCH((fd_dw_bwd1<T, K, S, MODE, ACT1, ACT2, ADD_SG, NL, true>), dim3((unsigned)a.d_gx, (unsigned)a.d_gy, (unsigned)c.p->B), dim3(256), lds1, c.s, a);
+            const dim3 grid((unsigned)a.d_gx, (unsigned)a.d_gy, B);
+            if (a.fin.rows) {
+                (void)hipFuncSetAttribute((const void *)fd_dw_bwd1<T, K, S, MODE, ACT1, ACT2, ADD_SG, NL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.blds);
+                FD_LAUNCH((fd_dw_bwd1<T, K, S, MODE, ACT1, ACT2, ADD_SG, NL, true>), grid, dim3(256), L.blds, c.s, a);
             } else {
-                (void)hipFuncSetAttribute((const void *)fd_dw_bwd1<T, K, S, MODE, ACT1, ACT2, ADD_SG, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-                FD_LAUNCH((fd_dw_bwd1<T, K, S, MODE, ACT1, ACT2, ADD_SG, NL, false>), dim3((unsigned)a.d_gx, (unsigned)a.d_gy, (unsigned)c.p->B), dim3(256), lds1, c.s, a);
+                (void)hipFuncSetAttribute((const void *)fd_dw_bwd1<T, K, S, MODE, ACT1, ACT2, ADD_SG, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.blds);
+                FD_LAUNCH((fd_dw_bwd1<T, K, S, MODE, ACT1, ACT2, ADD_SG, NL, false>), grid, dim3(256), L.blds, c.s, a);
             }
         });
-        int rc1 = check_launch("fd_dw_bwd1");
-        if (rc1) return rc1;
-        *nblk_out = a.d_gx * c.p->B;
-        return defer_weights(c, a.wpart, wblk1, kk * L.d.cin, kk, L.d.cin, c.grads[i].conv_weight);
+        return check_launch("fd_dw_bwd1");
+    case F::PAIR:                                             // both roles in one launch
+        fd_by_lane_width<T>(L.dw_n, [&](auto nt) {
+            constexpr int NL = decltype(nt)::value;
+            const dim3 grid((unsigned)(B * ((long)a.d_gx * a.d_gy + (long)a.w_gx * a.w_gy)));
+            if (a.fin.rows) {
+                if (L.blds > 64 * 1024) (void)hipFuncSetAttribute((const void *)fd_dw_bwd<T, K, S, MODE, ACT1, ACT2, ADD_SG, NL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.blds);
+                FD_LAUNCH((fd_dw_bwd<T, K, S, MODE, ACT1, ACT2, ADD_SG, NL, true>), grid, dim3(256), L.blds, c.s, a);
+            } else {
+                if (L.blds > 64 * 1024) (void)hipFuncSetAttribute((const void *)fd_dw_bwd<T, K, S, MODE, ACT1, ACT2, ADD_SG, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.blds);
+                FD_LAUNCH((fd_dw_bwd<T, K, S, MODE, ACT1, ACT2, ADD_SG, NL, false>), grid, dim3(256), L.blds, c.s, a);
+            }
+        });
+        return check_launch("fd_dw_bwd");
+    case F::SEPARATE: break;
     }
-    const int wblk = a.w_gx * c.p->B;
-    if ((size_t)wblk * kk * L.d.cin > L.wp_elems) return fail(FD_ERR_STATE, "depthwise weight-gradient partial region too small");
-    if (L.bwd_fin_rows) a.fin = bwd_fin_args(c, i, lds - (size_t)4 * cb * 4);
-    a.sr = bwd_rows(c.p, L.d.src, (long)a.d_gx * c.p->B);
-    const long total = (long)c.p->B * ((long)a.d_gx * a.d_gy + (long)a.w_gx * a.w_gy);
-    fd_by_lane_width<T>(L.dw_n, [&](auto nt) {
-        constexpr int NL = decltype(nt)::value;
-        if (a.fin.rows) {
-            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)fd_dw_bwd<T, K, S, MODE, ACT1, ACT2, ADD_SG, NL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            FD_LAUNCH((fd_dw_bwd<T, K, S, MODE, ACT1, ACT2, ADD_SG, NL, true>), dim3((unsigned)total), dim3(256), lds, c.s, a);
-        } else {
-            if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)fd_dw_bwd<T, K, S, MODE, ACT1, ACT2, ADD_SG, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            FD_LAUNCH((fd_dw_bwd<T, K, S, MODE, ACT1, ACT2, ADD_SG, NL, false>), dim3((unsigned)total), dim3(256), lds, c.s, a);
-        }
-    });
-    int rc = check_launch("fd_dw_bwd");
-    if (rc) return rc;
-    *nblk_out = a.d_gx * c.p->B;
-    return defer_weights(c, a.wpart, wblk, kk * L.d.cin, kk, L.d.cin, c.grads[i].conv_weight);
+    return fail(FD_ERR_STATE, "train: depthwise unit %d has no instance of its backward form %d", i, (int)L.bwd);
 }
 
 template <typename T>
-int dispatch_dw_bwd_pair(BwdCtx &c, int i, int *nblk, bool *paired)
+int launch_dw_bwd(BwdCtx &c, int i)
 {
-    const TLayer &L = c.p->layers[i];
-    const TLayer &P = c.p->layers[L.d.src];
-    const int a1 = P.d.act, a2 = L.d.skip >= 0 ? c.p->layers[L.d.skip].d.act : FD_ACT_RELU6;
-    const bool add = P.skip_consumer >= 0 && L.mode == 0;
-    const int key = L.d.ksize * 100 + L.d.stride * 10 + L.mode;
-    *paired = true;
-    if (a1 == FD_ACT_RELU6 && !add) {
-        if (key == 310) return launch_dw_bwd_pair<T, 3, 1, 0, FD_ACT_RELU6_, FD_ACT_RELU6_, 0>(c, i, nblk);
-        if (key == 320) return launch_dw_bwd_pair<T, 3, 2, 0, FD_ACT_RELU6_, FD_ACT_RELU6_, 0>(c, i, nblk);
-        if (key == 510) return launch_dw_bwd_pair<T, 5, 1, 0, FD_ACT_RELU6_, FD_ACT_RELU6_, 0>(c, i, nblk);
-    }
-    if (a1 == FD_ACT_RELU6 && add && key == 320) return launch_dw_bwd_pair<T, 3, 2, 0, FD_ACT_RELU6_, FD_ACT_RELU6_, 1>(c, i, nblk);
-    if (a1 == FD_ACT_RELU && key == 511) return launch_dw_bwd_pair<T, 5, 1, 1, FD_ACT_RELU_, FD_ACT_RELU6_, 0>(c, i, nblk);
-    if (a1 == FD_ACT_RELU && a2 == FD_ACT_RELU6 && key == 512) return launch_dw_bwd_pair<T, 5, 1, 2, FD_ACT_RELU_, FD_ACT_RELU6_, 0>(c, i, nblk);
-    if (a1 == FD_ACT_RELU && a2 == FD_ACT_RELU6 && key == 513) return launch_dw_bwd_pair<T, 5, 1, 3, FD_ACT_RELU_, FD_ACT_RELU6_, 0>(c, i, nblk);
-    *paired = false;                                          // an unusual combination (sibling / custom plans): the two separate kernels cover it
-    return FD_OK;
+    if (c.p->layers[i].bwd == TLayer::DwBwd::SEPARATE) return launch_dw_separate<T>(c, i);
+    int rc = FD_ERR_STATE;
+    fd_by_dw_instance(c.p, i, [&](auto in) {
+        using I = decltype(in);
+        rc = launch_dw_form<T, I::K, I::S, I::MODE, I::ACT1, I::ACT2, I::ADD_SG>(c, i);
+    });
+    return rc ? rc : defer_dw_weights(c, i);
 }
 
 template <typename T, int ACT_IN>
-int launch_pw_bwd_h16(BwdCtx &c, int i, int *nblk)
+int launch_pw_bwd_h16(BwdCtx &c, int i)
 {
     TLayer &L = c.p->layers[i];
     TLayer &P = c.p->layers[L.d.src];
@@ -426,7 +281,6 @@ int launch_pw_bwd_h16(BwdCtx &c, int i, int *nblk)
     const size_t lds_d = FD_PW_DGRAD_H16_RING(L.n64, tn) + (size_t)4 * 64 * tn * 4;     // ring of min(3, N tiles) stages (>= the epilogue's fp32 tiles) + statistics
     const bool add = P.skip_consumer >= 0;
     const unsigned n_dgrad = (unsigned)((m_tiles + 7) / 8 * 8 * k_tiles);
-    *nblk = m_tiles;
     if (pair) {
         const size_t lds = std::max(lds_d, FD_PW_WGRAD_H16_LDS(1));
         const int tiles_w = n_tiles * k_tiles_w;
@@ -434,7 +288,7 @@ int launch_pw_bwd_h16(BwdCtx &c, int i, int *nblk)
     do {                                                                                                                                           \
         (void)hipFuncSetAttribute((const void *)fd_pw_bwd_h16<T, ACT_IN, ADDV, TNV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);        \
         FD_LAUNCH((fd_pw_bwd_h16<T, ACT_IN, ADDV, TNV>), dim3(n_dgrad + (unsigned)(tiles_w * splits)), dim3(256), lds, c.s, G, twt<T>(c.p, L.wtt_off), twt<T>(c.p, P.z_off), \
-                  tws(c.p, P.st_off), ADDV ? twt<T>(c.p, P.sg_off) : (const T *)nullptr, twt<T>(c.p, P.g_off), bwd_rows(c.p, L.d.src, m_tiles), tws(c.p, L.wp_off), M, N, K, L.n64, \
+                  tws(c.p, P.st_off), ADDV ? twt<T>(c.p, P.sg_off) : (const T *)nullptr, twt<T>(c.p, P.g_off), bwd_rows(c.p, L.d.src), tws(c.p, L.wp_off), M, N, K, L.n64, \
                   m_tiles, k_tiles, (int)n_dgrad, k_tiles_w, tiles_w, rows, (FD_PW_BWD_W_FIRST && (unsigned)(tiles_w * splits) < n_dgrad) ? tiles_w * splits : 0); \
     } while (0)
         if (add) { if (tn == 2) FD_PWBWD_H16(1, 2); else FD_PWBWD_H16(1, 1); }
@@ -457,7 +311,7 @@ int launch_pw_bwd_h16(BwdCtx &c, int i, int *nblk)
     do {                                                                                                                                           \
         (void)hipFuncSetAttribute((const void *)fd_pw_dgrad_h16<T, ACT_IN, ADDV, TNV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);    \
         FD_LAUNCH((fd_pw_dgrad_h16<T, ACT_IN, ADDV, TNV>), grid, dim3(256), lds_d, c.s, G, twt<T>(c.p, L.wtt_off), twt<T>(c.p, P.z_off), tws(c.p, P.st_off), \
-                  ADDV ? twt<T>(c.p, P.sg_off) : (const T *)nullptr, twt<T>(c.p, P.g_off), bwd_rows(c.p, L.d.src, m_tiles), M, N, K, L.n64, m_tiles, k_tiles);          \
+                  ADDV ? twt<T>(c.p, P.sg_off) : (const T *)nullptr, twt<T>(c.p, P.g_off), bwd_rows(c.p, L.d.src), M, N, K, L.n64, m_tiles, k_tiles);          \
     } while (0)
         if (add) { if (tn == 2) FD_DGRAD_H16(1, 2); else FD_DGRAD_H16(1, 1); }
         else { if (tn == 2) FD_DGRAD_H16(0, 2); else FD_DGRAD_H16(0, 1); }
@@ -467,7 +321,7 @@ int launch_pw_bwd_h16(BwdCtx &c, int i, int *nblk)
 }
 
 template <int ACT_IN>
-int launch_pw_bwd(BwdCtx &c, int i, int *nblk)
+int launch_pw_bwd(BwdCtx &c, int i)
 {
     TLayer &L = c.p->layers[i];
     TLayer &P = c.p->layers[L.d.src];
@@ -484,7 +338,6 @@ int launch_pw_bwd(BwdCtx &c, int i, int *nblk)
     const size_t lds_d = ((size_t)FD_BWD_STAGES * (2 * 64 * 32 + 32 * 64) + 4 * N32 + 256) * 4;
     const bool add = P.skip_consumer >= 0;
     const unsigned n_dgrad = (unsigned)((m_tiles + 7) / 8 * 8 * k_tiles);
-    *nblk = m_tiles;
     int rc;
     if (!(c.p->flags & FD_PLAN_NO_BWD_PAIRING) && !(c.p->tune & FD_TUNE_NO_PW_PAIRING)) {
         const size_t lds = std::max(lds_w, lds_d);
@@ -494,11 +347,11 @@ int launch_pw_bwd(BwdCtx &c, int i, int *nblk)
         if (add) {
             (void)hipFuncSetAttribute((const void *)fd_pw_bwd_f32<ACT_IN, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             FD_LAUNCH((fd_pw_bwd_f32<ACT_IN, 1>), grid, dim3(256), lds, c.s, G, Z, coef, c.params[i].conv_weight, tws(c.p, P.z_off), tws(c.p, P.st_off),
-                      tws(c.p, P.sg_off), tws(c.p, P.g_off), bwd_rows(c.p, L.d.src, m_tiles), tws(c.p, L.wp_off), M, N, K, m_tiles, k_tiles, (int)n_dgrad, tiles_w, rows, n_w);
+                      tws(c.p, P.sg_off), tws(c.p, P.g_off), bwd_rows(c.p, L.d.src), tws(c.p, L.wp_off), M, N, K, m_tiles, k_tiles, (int)n_dgrad, tiles_w, rows, n_w);
         } else {
             (void)hipFuncSetAttribute((const void *)fd_pw_bwd_f32<ACT_IN, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             FD_LAUNCH((fd_pw_bwd_f32<ACT_IN, 0>), grid, dim3(256), lds, c.s, G, Z, coef, c.params[i].conv_weight, tws(c.p, P.z_off), tws(c.p, P.st_off),
-                      (const float *)nullptr, tws(c.p, P.g_off), bwd_rows(c.p, L.d.src, m_tiles), tws(c.p, L.wp_off), M, N, K, m_tiles, k_tiles, (int)n_dgrad, tiles_w, rows, n_w);
+                      (const float *)nullptr, tws(c.p, P.g_off), bwd_rows(c.p, L.d.src), tws(c.p, L.wp_off), M, N, K, m_tiles, k_tiles, (int)n_dgrad, tiles_w, rows, n_w);
         }
         if ((rc = check_launch("fd_pw_bwd_f32"))) return rc;
         return defer_weights(c, tws(c.p, L.wp_off), splits, N * K, 0, 0, c.grads[i].conv_weight);
@@ -515,11 +368,11 @@ int launch_pw_bwd(BwdCtx &c, int i, int *nblk)
         if (add) {
             (void)hipFuncSetAttribute((const void *)fd_pw_dgrad_f32<ACT_IN, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
             FD_LAUNCH((fd_pw_dgrad_f32<ACT_IN, 1>), grid, dim3(256), lds_d, c.s, G, Z, coef, c.params[i].conv_weight, tws(c.p, P.z_off), tws(c.p, P.st_off),
-                      tws(c.p, P.sg_off), tws(c.p, P.g_off), bwd_rows(c.p, L.d.src, m_tiles), M, N, K, m_tiles, k_tiles);
+                      tws(c.p, P.sg_off), tws(c.p, P.g_off), bwd_rows(c.p, L.d.src), M, N, K, m_tiles, k_tiles);
         } else {
             (void)hipFuncSetAttribute((const void *)fd_pw_dgrad_f32<ACT_IN, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
             FD_LAUNCH((fd_pw_dgrad_f32<ACT_IN, 0>), grid, dim3(256), lds_d, c.s, G, Z, coef, c.params[i].conv_weight, tws(c.p, P.z_off), tws(c.p, P.st_off),
-                      (const float *)nullptr, tws(c.p, P.g_off), bwd_rows(c.p, L.d.src, m_tiles), M, N, K, m_tiles, k_tiles);
+                      (const float *)nullptr, tws(c.p, P.g_off), bwd_rows(c.p, L.d.src), M, N, K, m_tiles, k_tiles);
         }
         return check_launch("fd_pw_dgrad_f32");
     }
@@ -545,8 +398,8 @@ int train_backward_t(fd_train_plan *plan, const fd_layer_params *params, const f
         }
         plan->bwd_stats_clean = false;
         const int nb = std::min(ceil_div(Hd.M, 256), 512);     // (grid-stride: one addition to the head's single statistics channel per workgroup)
-        if (Hd.d.act == FD_ACT_RELU6) FD_LAUNCH((fd_head_bwd_reduce_f32<FD_ACT_RELU6_>), dim3(nb), dim3(256), 0, s, static_cast<const float *>(dy), tws(plan, Hd.z_off), tws(plan, Hd.st_off), tws(plan, Hd.g_off), bwd_rows(plan, hi, nb), Hd.M, Hd.out_h, Hd.out_w, Hd.d.upsample);
-        else FD_LAUNCH((fd_head_bwd_reduce_f32<FD_ACT_RELU_>), dim3(nb), dim3(256), 0, s, static_cast<const float *>(dy), tws(plan, Hd.z_off), tws(plan, Hd.st_off), tws(plan, Hd.g_off), bwd_rows(plan, hi, nb), Hd.M, Hd.out_h, Hd.out_w, Hd.d.upsample);
+        if (Hd.d.act == FD_ACT_RELU6) FD_LAUNCH((fd_head_bwd_reduce_f32<FD_ACT_RELU6_>), dim3(nb), dim3(256), 0, s, static_cast<const float *>(dy), tws(plan, Hd.z_off), tws(plan, Hd.st_off), tws(plan, Hd.g_off), bwd_rows(plan, hi), Hd.M, Hd.out_h, Hd.out_w, Hd.d.upsample);
+        else FD_LAUNCH((fd_head_bwd_reduce_f32<FD_ACT_RELU_>), dim3(nb), dim3(256), 0, s, static_cast<const float *>(dy), tws(plan, Hd.z_off), tws(plan, Hd.st_off), tws(plan, Hd.g_off), bwd_rows(plan, hi), Hd.M, Hd.out_h, Hd.out_w, Hd.d.upsample);
         if ((rc = check_launch("fd_head_bwd_reduce_f32"))) return rc;
         if ((rc = bn_bwd_finalize(c, hi))) return rc;
         constexpr int PPB = 16;
@@ -554,8 +407,8 @@ int train_backward_t(fd_train_plan *plan, const fd_layer_params *params, const f
         const size_t lds = (size_t)32 * Hd.d.cin * 3 * 4;
         float *wpart = tws(plan, Hd.wp_off);
         if ((size_t)nb2 * Hd.d.cin > Hd.wp_elems) return fail(FD_ERR_STATE, "weight-gradient partial region too small for the head");
-        if (Hp.d.act == FD_ACT_RELU6) FD_LAUNCH((fd_head_bwd<T, FD_ACT_RELU6_, PPB>), dim3(nb2), dim3(256), lds, s, tws(plan, Hd.g_off), tws(plan, Hd.z_off), tws(plan, Hd.coef_off), twt<T>(plan, Hp.z_off), tws(plan, Hp.st_off), params[hi].conv_weight, twt<T>(plan, Hp.g_off), bwd_rows(plan, Hd.d.src, nb2), wpart, Hd.M, Hd.d.cin);
-        else FD_LAUNCH((fd_head_bwd<T, FD_ACT_RELU_, PPB>), dim3(nb2), dim3(256), lds, s, tws(plan, Hd.g_off), tws(plan, Hd.z_off), tws(plan, Hd.coef_off), twt<T>(plan, Hp.z_off), tws(plan, Hp.st_off), params[hi].conv_weight, twt<T>(plan, Hp.g_off), bwd_rows(plan, Hd.d.src, nb2), wpart, Hd.M, Hd.d.cin);
+        if (Hp.d.act == FD_ACT_RELU6) FD_LAUNCH((fd_head_bwd<T, FD_ACT_RELU6_, PPB>), dim3(nb2), dim3(256), lds, s, tws(plan, Hd.g_off), tws(plan, Hd.z_off), tws(plan, Hd.coef_off), twt<T>(plan, Hp.z_off), tws(plan, Hp.st_off), params[hi].conv_weight, twt<T>(plan, Hp.g_off), bwd_rows(plan, Hd.d.src), wpart, Hd.M, Hd.d.cin);
+        else FD_LAUNCH((fd_head_bwd<T, FD_ACT_RELU_, PPB>), dim3(nb2), dim3(256), lds, s, tws(plan, Hd.g_off), tws(plan, Hd.z_off), tws(plan, Hd.coef_off), twt<T>(plan, Hp.z_off), tws(plan, Hp.st_off), params[hi].conv_weight, twt<T>(plan, Hp.g_off), bwd_rows(plan, Hd.d.src), wpart, Hd.M, Hd.d.cin);
         if ((rc = check_launch("fd_head_bwd"))) return rc;
         if ((rc = defer_weights(c, wpart, nb2, Hd.d.cin, 0, 0, grads[hi].conv_weight))) return rc;
         // the BatchNorm partial sums of the head's producer are in its statistics rows
@@ -565,7 +418,6 @@ int train_backward_t(fd_train_plan *plan, const fd_layer_params *params, const f
     for (int i = std::min(hi - 1, (int)from_layer); i >= to_layer; --i) {
         TLayer &L = plan->layers[i];
         const fd_layer_desc &d = L.d;
-        int nblk = 0;
         fd_hs().trace_layer = i;
         switch (d.op) {
         case FD_OP_STEM: {
@@ -575,12 +427,11 @@ int train_backward_t(fd_train_plan *plan, const fd_layer_params *params, const f
             float *wpart = tws(plan, L.wp_off);
             if constexpr (!F32) {
                 // 16-bit plans, the 32-channel stem: row-walking fp32 kernel (fd_kernels_dw5p_bwd.h: fd_stem_wgrad_rows), one partial row per workgroup
-                if (L.dw3_groups) {
-                    const int wgs = ceil_div((long)L.dw3_groups * ceil_div(L.out_h, L.dw3_bh), 4), rows_w = wgs * plan->B;
-                    if ((size_t)rows_w * 27 * d.cout > L.wp_elems) return fail(FD_ERR_STATE, "stem weight-gradient partial region too small");
+                if (L.stemw_groups) {
+                    const int wgs = ceil_div((long)L.stemw_groups * ceil_div(L.out_h, L.stemw_bh), 4), rows_w = wgs * plan->B;
 #define FD_STEMW(CL_)                                                                                                                                     \
     FD_LAUNCH((fd_stem_wgrad_rows<T, CL_, FD_STEMW_CPL>), dim3((unsigned)wgs, (unsigned)plan->B), dim3(256), 0, s, static_cast<const float *>(plan->x_saved), twt<T>(plan, L.g_off), \
-              twt<T>(plan, L.z_off), tws(plan, L.coef_off), wpart, L.in_h, L.in_w, L.dw3_groups, L.dw3_bh)
+              twt<T>(plan, L.z_off), tws(plan, L.coef_off), wpart, L.in_h, L.in_w, L.stemw_groups, L.stemw_bh)
                     if (d.cout == 32) FD_STEMW(32 / FD_STEMW_CPL); else if (d.cout == 16) FD_STEMW(16 / FD_STEMW_CPL); else FD_STEMW(8 / FD_STEMW_CPL);
 #undef FD_STEMW
                     if ((rc = check_launch("fd_stem_wgrad_rows"))) return rc;
@@ -593,28 +444,13 @@ int train_backward_t(fd_train_plan *plan, const fd_layer_params *params, const f
             if ((rc = defer_weights(c, wpart, nb_w, 27 * d.cout, 0, 0, grads[i].conv_weight))) return rc;
             break;
         }
-        case FD_OP_DW: {
-            if (!(plan->flags & FD_PLAN_NO_BWD_PAIRING)) {
-                bool paired = false;
-                if ((rc = dispatch_dw_bwd_pair<T>(c, i, &nblk, &paired))) return rc;
-                if (paired) {
-                    if ((rc = finalize_or_defer(c, d.src))) return rc;
-                    break;
-                }
-            }
-            if ((rc = launch_dw_wgrad<T>(c, i))) return rc;
-            const TLayer &P = plan->layers[d.src];
-            const bool add = P.skip_consumer >= 0 && L.mode == 0;
-            if (P.d.act == FD_ACT_RELU6) rc = add ? dispatch_dw_dgrad<T, FD_ACT_RELU6_, 1>(c, i, &nblk) : dispatch_dw_dgrad<T, FD_ACT_RELU6_, 0>(c, i, &nblk);
-            else rc = add ? dispatch_dw_dgrad<T, FD_ACT_RELU_, 1>(c, i, &nblk) : dispatch_dw_dgrad<T, FD_ACT_RELU_, 0>(c, i, &nblk);
-            if (rc) return rc;
-            if ((rc = finalize_or_defer(c, d.src))) return rc;
+        case FD_OP_DW:
+            if ((rc = launch_dw_bwd<T>(c, i)) || (rc = finalize_or_defer(c, d.src))) return rc;
             break;
-        }
         case FD_OP_PW: {
             const TLayer &P = plan->layers[d.src];
-            if constexpr (F32) rc = P.d.act == FD_ACT_RELU6 ? launch_pw_bwd<FD_ACT_RELU6_>(c, i, &nblk) : launch_pw_bwd<FD_ACT_RELU_>(c, i, &nblk);
-            else rc = P.d.act == FD_ACT_RELU6 ? launch_pw_bwd_h16<T, FD_ACT_RELU6_>(c, i, &nblk) : launch_pw_bwd_h16<T, FD_ACT_RELU_>(c, i, &nblk);
+            if constexpr (F32) rc = P.d.act == FD_ACT_RELU6 ? launch_pw_bwd<FD_ACT_RELU6_>(c, i) : launch_pw_bwd<FD_ACT_RELU_>(c, i);
+            else rc = P.d.act == FD_ACT_RELU6 ? launch_pw_bwd_h16<T, FD_ACT_RELU6_>(c, i) : launch_pw_bwd_h16<T, FD_ACT_RELU_>(c, i);
             if (rc) return rc;
             if ((rc = finalize_or_defer(c, d.src))) return rc;
             break;

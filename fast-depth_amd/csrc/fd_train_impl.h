@@ -8,30 +8,29 @@ template <typename T, int ACT1, int ACT2>
 int launch_dw_train(const TLayer &L, const T *zin, const float *st1, const T *zskip, const float *st2, const float *w,
                     T *zout, fd_stat_rows part, hipStream_t s, int batch, const fd_bn_fin &fin)
 {
-    L.lds_rounding = (L.lds_rounding & ~(1 | 4)) | ((!L.rows_th && L.dw_n == 8) ? 1 : 0);
-    if (L.dw5_groups) {                                       // 16-bit plans, 5x5 on up2 + skip: row-walking pixel-pair kernel (input AND taps rounded to the storage type)
+    using F = TLayer::DwFwd;
+    if (L.fwd == F::ROWS5) {                                  // 16-bit plans, 5x5 on up2 + skip: row-walking pixel-pair kernel (input AND taps rounded to the storage type)
         if constexpr (!std::is_same<T, float>::value) {
-            L.lds_rounding |= 1 | 4;
-            FD_LAUNCH((fd_dw5_rows_train<T, ACT1, ACT2>), L.grid, dim3(256), 0, s, zin, st1, zskip, st2, w, zout, part, L.in_h, L.in_w, L.d.cin, L.dw5_groups, L.dw5_bh, fin);
+            FD_LAUNCH((fd_dw5_rows_train<T, ACT1, ACT2>), L.grid, dim3(256), 0, s, zin, st1, zskip, st2, w, zout, part, L.in_h, L.in_w, L.d.cin, L.rows_groups, L.rows_bh, fin);
             return check_launch("fd_dw5_rows_train");
         }
     }
-    if (L.dw3_cl) {                                           // 16-bit plans, 3x3 on a plain input: row-walking fp32-window kernel (nothing rounded but the stored output)
+    if (L.fwd == F::ROWS3) {                                  // 16-bit plans, 3x3 on a plain input: row-walking fp32-window kernel (nothing rounded but the stored output)
         if constexpr (!std::is_same<T, float>::value) {
-            const int key3 = L.d.stride * 100 + L.dw3_cl;
+            const int key3 = L.d.stride * 100 + L.rows_cl;
 #define FD_DW3F(S_, CL_)                                                                                                                                   \
     case S_ * 100 + CL_:                                                                                                                                  \
-        FD_LAUNCH((fd_dw3_rows_fwd<T, S_, ACT1, CL_>), L.grid, dim3(256), 0, s, zin, st1, w, zout, part, L.in_h, L.in_w, L.out_h, L.out_w, L.d.cin, L.dw3_groups, L.dw3_bh, fin); \
+        FD_LAUNCH((fd_dw3_rows_fwd<T, S_, ACT1, CL_>), L.grid, dim3(256), 0, s, zin, st1, w, zout, part, L.in_h, L.in_w, L.out_h, L.out_w, L.d.cin, L.rows_groups, L.rows_bh, fin); \
         break;
             switch (key3) {
                 FD_DW3F(1, 16) FD_DW3F(1, 32) FD_DW3F(2, 16) FD_DW3F(2, 32)
-            default: return fail(FD_ERR_STATE, "train: fd_dw3_rows_fwd has no instance for stride %d, %d channel lanes", L.d.stride, L.dw3_cl);
+            default: return fail(FD_ERR_STATE, "train: fd_dw3_rows_fwd has no instance for stride %d, %d channel lanes", L.d.stride, L.rows_cl);
             }
 #undef FD_DW3F
             return check_launch("fd_dw3_rows_fwd");
         }
     }
-    if (L.rows_th) {                                          // register-window kernel (3x3, plain input, large maps)
+    if (L.fwd == F::REGWIN) {                                 // register-window kernel (3x3, plain input, large maps)
         if (L.d.stride == 1) FD_LAUNCH((fd_dw3_rows_train<T, 1, ACT1>), L.grid, dim3(256), 0, s, zin, st1, w, zout, part, L.in_h, L.in_w, L.out_h, L.out_w, L.d.cin, L.rows_th, fin);
         else FD_LAUNCH((fd_dw3_rows_train<T, 2, ACT1>), L.grid, dim3(256), 0, s, zin, st1, w, zout, part, L.in_h, L.in_w, L.out_h, L.out_w, L.d.cin, L.rows_th, fin);
         return check_launch("fd_dw3_rows_train");
@@ -196,6 +195,154 @@ int train_forward_t(fd_train_plan *plan, const fd_layer_params *params, int32_t 
     return FD_OK;
 }
 
+// input rows per backward-data tile: balanced over the map (14 -> 7 + 7 instead of 8 + 6: both tiles full, smaller patches, one more workgroup per
+// CU); the upsampled modes produce 2 x 2 blocks per low-resolution pixel and need an even count
+inline int dw_dgrad_rows(const fd_train_plan *p, const TLayer &L)
+{
+    if (p->tune & FD_TUNE_DW_TH8) return 8;
+    // 3x3 stride-1 units: 14 rows where they divide the map (same reasoning as the forward kernel's larger tiles: fewer, fatter workgroups; the
+    // dz patch of 16 x 18 pixels = 41.5 KB stays below the 44.4 KB the paired weight-gradient role needs anyway)
+    // (measured, bf16 step: conv1 55.3 -> 52.1 us, conv3 59.2 -> 55.1, conv5 35.3 -> 32.7, 14x14 maps 20.5 -> 19.5)
+    if (L.d.ksize == 3 && L.d.stride == 1 && L.mode == 0 && L.in_h % 14 == 0) return 14;
+    const int th = ceil_div(L.in_h, ceil_div(L.in_h, L.d.ksize == 5 ? FD_T_DW5_DTH : (L.d.stride == 2 ? FD_T_S2_DTH : 8)));
+    return (L.mode != 0 || L.d.stride == 2) ? (th + 1) / 2 * 2 : th;     // (stride 2: the tile must hold whole receptive-field rows of its owned outputs)
+}
+// Rows (columns) of the dz patch that an INPUT-space tile of t rows (columns, a multiple of the stride, starting on a multiple of it) reads: the
+// EXACT extent the kernel computes (fd_dw_dgrad_body: PH, PW) -- stride 1: t + K - 1; stride 2: t / 2 + 2.  (Rounds 1-2 requested up to 4 rows and
+// columns more: 58 KB instead of 38 for the 5x5 units = 2 resident workgroups per CU instead of 4.)
+inline int dw_dz_patch(int t, int k, int s) { return (t + k - 2) / s + (s == 2 ? 2 : 1); }
+
+#ifndef FD_DW_ROWS_FIN
+#define FD_DW_ROWS_FIN 1               // the row-walking backward kernels finalise their unit's BatchNorm backward in the prologue (0: the separate launch; A/B switch)
+#endif
+#ifndef FD_DW3_ROWS_MIN_PIXELS
+#define FD_DW3_ROWS_MIN_PIXELS 0      // maps below this many pixels keep the paired LDS-tiled launch (tools/build_variant.py A/B switch)
+#endif
+#ifndef FD_DW3_ROWS_SMALL_BAND
+#define FD_DW3_ROWS_SMALL_BAND 7
+#endif
+// The backward form of depthwise unit i (TLayer::bwd) and its geometry; the weight-gradient partial rows it leaves size wp_elems.
+// Plan-time LDS without the in-kernel finalisation's coefficient block (added once the statistics row counts are known).
+void dw_bwd_plan(fd_train_plan *p, int i)
+{
+    using F = TLayer::DwBwd;
+    TLayer &L = p->layers[i];
+    const fd_layer_desc &d = L.d;
+    const uint32_t tune = p->tune;
+    const int K = d.ksize, S = d.stride, B = p->B, cb = L.dw_n << L.cbq, le = L.dw_n == 8 ? 2 : 4, ncb = ceil_div(d.cin, cb), cgn = d.cin / 4;
+    const bool add = p->layers[d.src].skip_consumer >= 0 && L.mode == 0, k3s1 = K == 3 && S == 1 && L.mode == 0, k3s2 = K == 3 && S == 2 && L.mode == 0;
+    // 16-bit plans: the row-walking kernels of fd_kernels_dw5p_bwd.h, each with the tune flags that keep it off
+    const bool rk = p->esz == 2 && d.cin % 8 == 0 && (double)L.in_h * L.in_w * d.cin * 2.0 < 2147483648.0 && !(tune & (FD_TUNE_NO_DW5_ROWS | FD_TUNE_DW_BWD1 | FD_TUNE_DW_BWD_PAIR));
+    if ((p->flags & FD_PLAN_NO_BWD_PAIRING) || !fd_by_dw_instance(p, i, [](auto) {})) L.bwd = F::SEPARATE;
+    // 5x5 on up2 + skip (decode_conv3 / 4 / 5 .0): both gradients on the pixel-pair kernel fd_dw5_bwd_rows -- one launch, backward-data workgroups first, then the
+    // weight-gradient workgroups of the same image (same XCD: the second role finds G / z in its L2)
+    else if (rk && K == 5 && S == 1 && L.mode == 2 && L.in_w % 4 == 0 && L.in_h % 2 == 0) L.bwd = F::ROWS5;
+    // 3x3 stride 1 on plain inputs (conv1.0 / conv3.0 / conv5.0 / the 14x14 units ...): fd_dw3_bwd_rows (fp32 window: nothing rounded)
+    else if (rk && !(tune & FD_TUNE_FORCE_DW_H8) && k3s1 && !add && (long)L.in_h * L.in_w >= FD_DW3_ROWS_MIN_PIXELS) L.bwd = F::ROWS3;
+    // 3x3 stride 2 (conv2.0 / conv4.0 / conv6.0 / conv12.0): ONE pass over z_in, G, z and the skip gradient produces both gradients (fd_dw3s2_bwd_rows); these
+    // units are byte-bound and the paired forms read their operands twice
+    else if (rk && !(tune & (FD_TUNE_FORCE_DW_H8 | FD_TUNE_DW_FORCE_ROWS | FD_TUNE_DW_NO_ROWS)) && k3s2 && L.in_h == 2 * L.out_h && L.in_w == 2 * L.out_w) L.bwd = F::ROWS3S2;
+    // The stride-2 3x3 units of the large maps (channel-group count a power of two in 8 ... 64): two register-window kernels without LDS staging
+    // (fd_dw3s2_dgrad_rows over input columns, fd_dw3_wgrad_rows over output columns).  Measured (us, rows pair vs single-staging kernel): bf16 conv2.0
+    // 48.9 + 16.8 vs 79.3, conv4.0 33.4 + 11.0 vs 48.2, conv6.0 (14x14 outputs) 23.4 + 7.8 vs 29.6; fp32 conv2.0 69.0 + 26.7 vs 96.2, conv4.0 40.7 + 15.3 vs
+    // 55.2 (equal: both forms move the fp32 bytes at the same rate) -> 16-bit plans, maps >= 28x28
+    else if (k3s2 && cgn >= 8 && cgn <= 64 && (cgn & (cgn - 1)) == 0 && (((long)L.out_h * L.out_w >= 28 * 28 && p->esz == 2) || (tune & FD_TUNE_DW_FORCE_ROWS)) &&
+             !(tune & (FD_TUNE_DW_NO_ROWS | FD_TUNE_DW_BWD_PAIR | FD_TUNE_DW_BWD1))) L.bwd = F::REGWIN_S2;
+    // (stride-1 3x3 units: the LDS-tiled backward-data kernel on its own + fd_dw3_wgrad_rows instead of the paired launch measured equal -- conv1.0
+    // 31.2 + 20.3 vs 52.8 us, conv3.0 34.8 + 20.5 vs 56.4, conv5.0 22.1 + 14.6 vs 33.1 -- the pair stays)
+    // measured (bf16, batch 32): the single-staging kernel fd_dw_bwd1 wins on the stride-2 units (conv2.0 84 vs 103 us, conv4.0 50 vs 57, conv6.0 31 vs 35) and
+    // loses on the stride-1 3x3 ones (conv1.0 68 vs 57, 14x14 maps 22.4 vs 19.5: two tap phases back to back in one workgroup at lower residency);
+    // the 5x5 units tie.  FD_TUNE_DW_BWD1 forces it everywhere (tests), FD_TUNE_DW_BWD_PAIR nowhere.
+    else if (!(tune & FD_TUNE_DW_BWD_PAIR) && (S == 2 || (tune & FD_TUNE_DW_BWD1))) L.bwd = F::BWD1;
+    else L.bwd = F::PAIR;
+    // the LDS-tiled kernels: backward data on input-space tiles, backward weights on output-space tiles -- as many per workgroup (along x) as keep
+    // >= ~1536 workgroups in flight (the pair keeps roughly the same number of workgroups in flight per role)
+    L.d_th = dw_dgrad_rows(p, L); L.d_tw = K == 5 ? FD_T_DW5_DTW : (S == 2 ? FD_T_S2_DTW : 16);
+    L.d_tiles_x = ceil_div(L.in_w, L.d_tw); L.d_gx = L.d_tiles_x * ceil_div(L.in_h, L.d_th);
+    L.w_tiles_x = ceil_div(L.out_w, L.btw);
+    const int bty = ceil_div(L.out_h, L.bth);
+    L.w_tpw = (tune & FD_TUNE_WGRAD_TILE_ROWS) ? L.w_tiles_x : std::max(1, std::min(L.w_tiles_x, (int)((long)L.w_tiles_x * bty * ncb * B / FD_DW_WGRAD_TARGET_WGS)));
+    const int groups_x = ceil_div(L.w_tiles_x, L.w_tpw);
+    L.w_tpw = ceil_div(L.w_tiles_x, groups_x); L.w_gx = groups_x * bty;
+    const size_t lds_d = lds_patch_bytes((long)dw_dz_patch(L.d_th, K, S) * dw_dz_patch(L.d_tw, K, S), L.bpstr, le) + (size_t)K * K * cb * 4;
+    // (weights: activated input patch + dz tile, both [pixels][cb + pad]; the final reduction (npt/K groups x K*K taps x cb) reuses it)
+    const size_t lds_w = std::max(lds_patch_bytes((long)((L.bth - 1) * S + K) * ((L.btw - 1) * S + K) + L.bth * L.btw, L.bpstr, le), (size_t)((256 >> L.cbq) / K) * K * K * cb * 4);
+    long wrows = 0;                                           // weight-gradient partial rows
+    switch (L.bwd) {
+    case F::ROWS5: {
+        L.rb_groups = ceil_div(L.in_w, 8);
+        const int bands = std::max(1, (L.in_h + 7) / 14);
+        L.rb_bh = ceil_div(ceil_div(L.in_h, bands), 2) * 2;
+        L.rb_wgs = ceil_div((long)L.rb_groups * ceil_div(L.in_h, L.rb_bh), 4);
+        L.nblk_b = wrows = (long)L.rb_wgs * B;
+        break;
+    }
+    case F::ROWS3: {
+        L.rb_cl = d.cin <= 32 ? 16 : 32;                      // channel lanes per strip: a 32-channel unit (conv1.0) would leave half of every wave idle at 32
+        L.rb_groups = ceil_div(L.in_w, 4 * (64 / L.rb_cl));
+        // bands of ~14 rows on the large maps; the 14x14 / 7x7 maps take bands of 7 (twice the waves: their launches are latency-, not issue-bound)
+        const int bands = L.in_h <= 7 ? ceil_div(L.in_h, 4) : L.in_h <= 14 ? ceil_div(L.in_h, FD_DW3_ROWS_SMALL_BAND) : std::max(1, (L.in_h + 7) / 14);     // (7x7: 512 -> 1024 waves, -2.7 us)
+        L.rb_bh = ceil_div(L.in_h, bands);
+        L.rb_wgs = ceil_div((long)L.rb_groups * ceil_div(L.in_h, L.rb_bh), 4);
+        L.nblk_b = wrows = (long)L.rb_wgs * B;
+        break;
+    }
+    case F::ROWS3S2: {
+        L.rb_groups = ceil_div(L.out_w, 8);
+        const int bands = L.out_h <= 7 ? ceil_div(L.out_h, 2) : L.out_h <= 14 ? ceil_div(L.out_h, 4) : std::max(1, (L.out_h + 3) / 7);     // ~7 output rows (14 input rows) per band; the small maps take 4 / 2
+        L.rb_bh = ceil_div(L.out_h, bands);
+        L.rb_wgs = ceil_div((long)L.rb_groups * ceil_div(L.out_h, L.rb_bh), 4);
+        L.nblk_b = wrows = (long)L.rb_wgs * B;
+        break;
+    }
+    case F::REGWIN_S2: {                                      // row strips as high as still leave >= ~1024 workgroups
+        const int gxd = ceil_div((long)L.in_w * cgn, 256), h2 = L.in_h / 2, gxw = ceil_div((long)L.out_w * cgn, 256);
+        L.rw_th_d = h2;
+        while (L.rw_th_d > 2 && (long)gxd * ceil_div(h2, L.rw_th_d) * B < 1024) L.rw_th_d = (L.rw_th_d + 1) / 2;
+        L.rw_th_w = L.out_h;
+        while (L.rw_th_w > 4 && (long)gxw * ceil_div(L.out_h, L.rw_th_w) * B < 1024) L.rw_th_w = (L.rw_th_w + 1) / 2;
+        L.rw_grid_d = dim3(gxd, ceil_div(h2, L.rw_th_d), B);
+        L.rw_grid_w = dim3(gxw, ceil_div(L.out_h, L.rw_th_w), B);
+        L.nblk_b = (long)gxd * L.rw_grid_d.y * B;
+        wrows = (long)gxw * L.rw_grid_w.y * B;
+        break;
+    }
+    case F::BWD1: {                                           // ONE workgroup per input-space tile stages the dz patch and the forward-input patch once
+        const int th_in = (L.d_th / S - 1) * S + K, tw_in = (L.d_tw / S - 1) * S + K;
+        const int ph = (L.d_th + K - 2) / S + 2, pw = (L.d_tw + K - 2) / S + 2;          // upper bound of the dz patch
+        L.blds = align_up(std::max(lds_patch_bytes((long)ph * pw + th_in * tw_in, L.bpstr, le) + (size_t)K * K * cb * 4, (size_t)((256 >> L.cbq) / K) * K * K * cb * 4 + 8192), 16);
+        L.nblk_b = wrows = (long)L.d_gx * B;
+        break;
+    }
+    case F::PAIR:
+        L.blds = align_up(std::max(lds_d, lds_w), 16);
+        L.nblk_b = (long)L.d_gx * B;
+        wrows = (long)L.w_gx * B;
+        break;
+    case F::SEPARATE:
+        L.blds = lds_w; L.blds2 = lds_d;                      // fd_dw_wgrad / fd_dw_dgrad
+        L.nblk_b = (long)L.d_gx * B;
+        wrows = (long)L.w_gx * B;
+        break;
+    }
+    L.wp_elems = (size_t)wrows * K * K * d.cin;
+}
+
+// the unit's first backward kernel CAN finalise its BatchNorm backward (the LDS-tiled depthwise launches, the row-walking depthwise kernels, the apply pass
+// of the 16-bit pointwise units); it does so when its consumer leaves few statistics rows (fd_train_plan_create)
+bool bwd_fin_candidate(const fd_train_plan *p, int i)
+{
+    using F = TLayer::DwBwd;
+    const TLayer &L = p->layers[i];
+    if ((p->tune & FD_TUNE_NO_CONSUMER_FINALIZE) || L.head || L.d.src < 0) return false;
+    if (L.d.op == FD_OP_PW) return p->esz == 2;           // (16-bit plans: the apply pass fd_bn_bwd_apply_fin_h16; any row count now that the rows are few)
+    if (L.d.op != FD_OP_DW) return false;
+    if (bwd_on_row_kernel(L)) return FD_DW_ROWS_FIN;      // (round 6: the row-walking kernels derive the coefficients in their prologue -- no registers carried through the walk)
+    // (LDS-tiled launches: built and measured in round 4 with up to 128 fp32 partial rows, off by default -- bf16 step: the 10 launches it removed were 43 us, the
+    // paired kernels got 40 us slower (163 VGPRs + 36 bytes of scratch in the 3x3 instance); fp32 step +26 us.  FD_TUNE_DW_BWD_FINALIZE turns it on: tests, A/B)
+    return (p->tune & FD_TUNE_DW_BWD_FINALIZE) && (L.bwd == F::BWD1 || L.bwd == F::PAIR);
+}
+
 }  // namespace
 
 extern "C" {
@@ -260,18 +407,17 @@ int fd_train_plan_create(const fd_layer_desc *layers, int32_t n_layers, int32_t 
                 L.grid = dim3(bpi, batch);
                 L.nblk = bpi * batch;
             }
-            L.wp_elems = (size_t)std::min(L.nblk, 512) * 27 * d.cout;
             // 16-bit plans, 32 / 16 / 8 output channels: the backward-weights pass runs on the row-walking kernel fd_stem_wgrad_rows (bands of ~7 output rows, 16 output
-            // columns per wave); dw3_groups / dw3_bh carry its column groups per row and rows per band
+            // columns per wave), one partial row per workgroup; otherwise fd_stem_wgrad walks blocks of 256 pixels grid-stride on at most 512 workgroups
             if (h16 && (d.cout == 32 || d.cout == 16 || d.cout == 8) && L.out_w % 4 == 0 && L.in_h == 2 * L.out_h && L.in_w == 2 * L.out_w && !(tune & FD_TUNE_NO_DW5_ROWS)) {
-                L.dw3_groups = ceil_div(L.out_w, 4 * (64 / (d.cout / FD_STEMW_CPL)));     // a wave: cout / FD_STEMW_CPL channel lanes, the rest of its 64 lanes column groups of 4 output columns
-                L.dw3_bh = ceil_div(L.out_h, std::max(1, (L.out_h + FD_STEMW_BAND / 2) / FD_STEMW_BAND));
-                const long rows_w = (long)ceil_div((long)L.dw3_groups * ceil_div(L.out_h, L.dw3_bh), 4) * batch;
-                L.wp_elems = std::max(L.wp_elems, (size_t)rows_w * 27 * d.cout);
-            }
+                L.stemw_groups = ceil_div(L.out_w, 4 * (64 / (d.cout / FD_STEMW_CPL)));     // a wave: cout / FD_STEMW_CPL channel lanes, the rest of its 64 lanes column groups of 4 output columns
+                L.stemw_bh = ceil_div(L.out_h, std::max(1, (L.out_h + FD_STEMW_BAND / 2) / FD_STEMW_BAND));
+                L.wp_elems = (size_t)ceil_div((long)L.stemw_groups * ceil_div(L.out_h, L.stemw_bh), 4) * batch * 27 * d.cout;
+            } else L.wp_elems = (size_t)std::min(ceil_div((long)batch * L.out_h * L.out_w, 256), 512) * 27 * d.cout;
             break;
         case FD_OP_DW: {
             if (d.src < 0 || d.cin != d.cout || (d.ksize != 3 && d.ksize != 5) || (d.stride != 1 && d.stride != 2) || d.cin % 4) FD_BAD("layer %d: bad depthwise", i);
+            if (d.stride == 2 && (L.in_h % 2 || L.in_w % 2)) FD_BAD("layer %d: stride-2 depthwise on odd input", i);
             L.mode = d.upsample ? (d.skip >= 0 ? (concat ? 3 : 2) : 1) : 0;
             L.out_h = L.in_h / d.stride; L.out_w = L.in_w / d.stride;
             // bf16 plans CAN run these kernels with 8 channels (16 bytes) per work-item and LDS patches kept in bf16 (fd_lane<T, 8>: a 64-channel block
@@ -319,6 +465,7 @@ int fd_train_plan_create(const fd_layer_desc *layers, int32_t n_layers, int32_t 
                     const int gx = ceil_div((long)L.out_w * cg, 256);
                     int th = L.out_h;
                     while (th > 4 && (long)gx * ceil_div(L.out_h, th) * batch < 1024) th = (th + 1) / 2;
+                    L.fwd = TLayer::DwFwd::REGWIN;
                     L.rows_th = th;
                     L.grid = dim3(gx, ceil_div(L.out_h, th), batch);
                     L.nblk = gx * ceil_div(L.out_h, th) * batch;
@@ -328,10 +475,11 @@ int fd_train_plan_create(const fd_layer_desc *layers, int32_t n_layers, int32_t 
             // 16-bit plans, 5x5 on up2 + skip (decode_conv3 / 4 / 5 .0): the row-walking pixel-pair kernel (fd_kernels_dw5p_bwd.h: fd_dw5_rows_train); bands of ~14 rows
             if (h16 && k5 && d.stride == 1 && L.mode == 2 && L.out_w % 4 == 0 && L.in_h % 2 == 0 && d.cin % 8 == 0 && (double)L.in_h * L.in_w * d.cin * 2.0 < 2147483648.0 &&
                 !(tune & (FD_TUNE_NO_DW5_ROWS | FD_TUNE_FORCE_DW_H8))) {
-                L.dw5_groups = ceil_div(L.out_w, 8);
+                L.fwd = TLayer::DwFwd::ROWS5;
+                L.rows_groups = ceil_div(L.out_w, 8);
                 const int bands = std::max(1, (L.out_h + 7) / 14);
-                L.dw5_bh = ceil_div(ceil_div(L.out_h, bands), 2) * 2;
-                const int wgs = ceil_div((long)L.dw5_groups * ceil_div(L.out_h, L.dw5_bh), 4);
+                L.rows_bh = ceil_div(ceil_div(L.out_h, bands), 2) * 2;
+                const int wgs = ceil_div((long)L.rows_groups * ceil_div(L.out_h, L.rows_bh), 4);
                 L.grid = dim3(wgs, ceil_div(d.cin, 64), batch);
                 L.nblk = wgs * batch;
                 L.lds = 0;
@@ -341,31 +489,24 @@ int fd_train_plan_create(const fd_layer_desc *layers, int32_t n_layers, int32_t 
             if (h16 && d.ksize == 3 && L.mode == 0 && d.cin % 8 == 0 && (d.stride == 1 || (L.in_h % 2 == 0 && L.in_w % 2 == 0)) &&
                 (double)L.in_h * L.in_w * d.cin * 2.0 < 2147483648.0 &&
                 !(tune & (FD_TUNE_NO_DW5_ROWS | FD_TUNE_FORCE_DW_H8 | FD_TUNE_DW_NO_ROWS | FD_TUNE_DW_FORCE_ROWS))) {
-                L.rows_th = 0;
-                L.dw3_cl = d.cin <= 32 ? 16 : 32;                // (a 32-channel unit would leave half of every wave idle at 32 lanes per strip)
-                L.dw3_groups = ceil_div(L.out_w, 4 * (64 / L.dw3_cl));
+                L.fwd = TLayer::DwFwd::ROWS3;
+                L.rows_cl = d.cin <= 32 ? 16 : 32;               // (a 32-channel unit would leave half of every wave idle at 32 lanes per strip)
+                L.rows_groups = ceil_div(L.out_w, 4 * (64 / L.rows_cl));
                 const int tall = L.out_h <= 7 ? 4 : (L.out_h <= 14 ? 7 : (d.stride == 1 ? 14 : 7));
                 const int bands = std::max(1, (L.out_h + tall / 2) / tall);
-                L.dw3_bh = ceil_div(L.out_h, bands);
-                const int wgs = ceil_div((long)L.dw3_groups * ceil_div(L.out_h, L.dw3_bh), 4);
-                L.grid = dim3(wgs, ceil_div(d.cin, 2 * L.dw3_cl), batch);
+                L.rows_bh = ceil_div(L.out_h, bands);
+                const int wgs = ceil_div((long)L.rows_groups * ceil_div(L.out_h, L.rows_bh), 4);
+                L.grid = dim3(wgs, ceil_div(d.cin, 2 * L.rows_cl), batch);
                 L.nblk = wgs * batch;
                 L.lds = 0;
             }
-            if (L.mode != 3 && !(tune & FD_TUNE_NO_CONSUMER_FINALIZE) && !(L.rows_th && d.cin > 256) &&
-                p->layers[d.src].nr_f <= (L.rows_th ? FD_STAT_FIN_MAX_ROWS_ALL : ((L.dw3_cl || L.dw5_groups) ? FD_STAT_FIN_MAX_ROWS_ROWK : FD_STAT_FIN_MAX_ROWS_BLOCK))) {
+            using F = TLayer::DwFwd;
+            if (L.mode != 3 && !(tune & FD_TUNE_NO_CONSUMER_FINALIZE) && !(L.fwd == F::REGWIN && d.cin > 256) &&
+                p->layers[d.src].nr_f <= (L.fwd == F::REGWIN ? FD_STAT_FIN_MAX_ROWS_ALL : (L.fwd == F::TILED ? FD_STAT_FIN_MAX_ROWS_BLOCK : FD_STAT_FIN_MAX_ROWS_ROWK))) {
                 // the producer's BatchNorm is finalised by this kernel's workgroups from the producer's statistics rows (fd_stat_table_block in the LDS-tiled
                 // kernel, which keeps the block's (scale, shift) behind its tap table; the register-window kernel holds all C <= 256 channels in its static LDS)
                 p->layers[d.src].fin_by_consumer = true;
-                if (!L.rows_th && !L.dw5_groups && !L.dw3_cl) L.lds += (size_t)2 * cb * 4;
-            }
-            const int fwd_tiles = ceil_div(L.out_w, L.btw) * ceil_div(L.out_h, L.bth) * batch;      // (tiles of the separate backward-weights kernel)
-            {   // weight-gradient partial rows: one per forward tile (separate kernels) or one per INPUT-space backward tile (fd_dw_bwd1: 16 columns x
-                // up to 8 rows) -- sized for the larger count
-                const long bwd_tiles = (long)ceil_div(L.in_w, 16) * ceil_div(L.in_h, 6) * batch;
-                // (the register-window weight-gradient kernels: one row per 256 (column, channel group) pairs x strip of >= 4 rows)
-                const long rows_tiles = (long)ceil_div((long)L.out_w * (d.cin / 4), 256) * ceil_div(L.out_h, 4) * batch;
-                L.wp_elems = (size_t)std::max<long>(std::max<long>(fwd_tiles, bwd_tiles), rows_tiles) * d.ksize * d.ksize * d.cin;
+                if (L.fwd == F::TILED) L.lds += (size_t)2 * cb * 4;
             }
             break;
         }
@@ -453,10 +594,26 @@ int fd_train_plan_create(const fd_layer_desc *layers, int32_t n_layers, int32_t 
         L.nr_cap = L.head ? FD_STAT_MAX_ROWS : stat_nr(ceil_div(L.M, 64));       // (the head's single channel: one line per row, 512 workgroups)
         L.nr_f = L.head ? L.nr_cap : std::min(L.nr_cap, stat_nr(L.nblk));
         max_g = std::max(max_g, L.z_elems);
-        L.wp_off = off; off += align_up(std::max(L.wp_elems, (size_t)1) * 4, 256);
     }
     TLayer &last = p->layers.back();
-    if (!last.head || (last.d.upsample ? 2 * last.out_h : last.out_h) != height) FD_BAD("the last layer must be the 1-channel head producing [B,1,%d,%d]", height, width);
+    if (!last.head || (last.d.upsample ? 2 * last.out_h : last.out_h) != height || (last.d.upsample ? 2 * last.out_w : last.out_w) != width)
+        FD_BAD("the last layer must be the 1-channel head producing [B,1,%d,%d]", height, width);
+    // the backward form of every depthwise unit (it needs every unit's skip consumer), then the statistics rows each unit's consumer deals its
+    // backward partials to, and whether the unit's first backward kernel finalises its BatchNorm backward from them
+    for (int i = 0; i < n_layers; ++i)
+        if (p->layers[i].d.op == FD_OP_DW) dw_bwd_plan(p, i);
+    for (int i = 0; i < n_layers; ++i) {
+        TLayer &U = p->layers[i];
+        if (U.consumer >= 0) {
+            const TLayer &C = p->layers[U.consumer];
+            U.nr_b = std::min(U.nr_cap, stat_nr(C.head ? ceil_div(C.M, 32 * 16) : C.d.op == FD_OP_PW ? ceil_div(C.M, 64) : C.nblk_b));
+        } else if (U.head) U.nr_b = U.nr_cap;           // (the head's single channel: every row is a line of its own -- all of them)
+        if (bwd_fin_candidate(p, i) && U.nr_b <= (bwd_on_row_kernel(U) ? FD_STAT_FIN_MAX_ROWS_ROWK : FD_STAT_FIN_MAX_ROWS_BLOCK)) U.bwd_fin_rows = U.nr_b;
+        if (U.d.op != FD_OP_DW) continue;
+        if (U.bwd_fin_rows && (U.bwd == TLayer::DwBwd::BWD1 || U.bwd == TLayer::DwBwd::PAIR)) U.blds += (size_t)4 * (U.dw_n << U.cbq) * 4;     // + the coefficient block (fd_bn_bwd_fin::cf_off)
+        if (U.blds > (U.bwd == TLayer::DwBwd::SEPARATE ? 64 : 160) * 1024) FD_BAD("layer %d: depthwise backward LDS request %zu exceeds the limit", i, U.blds);
+    }
+    for (int i = 0; i < n_layers; ++i) { p->layers[i].wp_off = off; off += align_up(std::max(p->layers[i].wp_elems, (size_t)1) * 4, 256); }
 #undef FD_BAD
     // backward buffers: the gradient of unit i is consumed by unit i's own backward kernels right after unit i+1's, so two
     // ping-pong buffers suffice; skip sources get a private buffer for the decoder's contribution
@@ -486,7 +643,6 @@ int fd_train_plan_create(const fd_layer_desc *layers, int32_t n_layers, int32_t 
         TLayer &U = p->layers[i];
         if (U.fin_by_consumer && U.skip_consumer >= 0 && U.skip_consumer < U.consumer) U.fin_by_consumer = false;
     }
-    for (int i = 0; i < n_layers; ++i) p->layers[i].bwd_fin = bwd_fin_candidate(p, i);
     p->ws_bytes = off;
     *out_plan = p;
     return FD_OK;
@@ -518,14 +674,19 @@ int fd_train_forward(fd_train_plan *plan, const fd_layer_params *params, int32_t
 int fd_train_plan_lds_rounding(const fd_train_plan *plan, int32_t layer)
 {
     if (!plan || layer < 0 || layer >= (int)plan->layers.size()) return -1;
-    return plan->layers[layer].lds_rounding;
+    const TLayer &L = plan->layers[layer];
+    if (L.d.op != FD_OP_DW) return 0;
+    const bool h8 = L.dw_n == 8, tiled_bwd = L.bwd == TLayer::DwBwd::BWD1 || L.bwd == TLayer::DwBwd::PAIR || L.bwd == TLayer::DwBwd::SEPARATE;
+    return (L.fwd == TLayer::DwFwd::ROWS5 ? 1 | 4 : (L.fwd == TLayer::DwFwd::TILED && h8 ? 1 : 0)) | (L.bwd == TLayer::DwBwd::ROWS5 ? 2 | 8 : (tiled_bwd && h8 ? 2 : 0));
 }
 
 int fd_train_plan_unit_kernels(const fd_train_plan *plan, int32_t layer)
 {
     if (!plan || layer < 0 || layer >= (int)plan->layers.size()) return -1;
     const TLayer &L = plan->layers[layer];
-    return (L.pw16_tm ? 1 : 0) | (L.fin_by_consumer ? 2 : 0) | (L.bwd_fin_rows > 0 ? 4 : 0) | (L.bwd_rows ? 8 : 0) | (L.dw5_groups ? 16 : 0) | (L.dw3_cl ? 32 : 0);
+    const bool dw = L.d.op == FD_OP_DW;
+    return (L.pw16_tm ? 1 : 0) | (L.fin_by_consumer ? 2 : 0) | (L.bwd_fin_rows > 0 ? 4 : 0) | (bwd_on_row_kernel(L) ? 8 : 0) | (dw && L.fwd == TLayer::DwFwd::ROWS5 ? 16 : 0) |
+           (dw && L.fwd == TLayer::DwFwd::ROWS3 ? 32 : 0);
 }
 
 int fd_train_layer_tensor(const fd_train_plan *plan, int32_t layer, int32_t which, const void **device_ptr, int32_t *n, int32_t *h,

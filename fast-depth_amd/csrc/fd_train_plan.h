@@ -54,12 +54,22 @@ struct fd_train_layer {
     int csplit = 0;                  // concatenating depthwise consumer (mode 3): channels [0, csplit) come from src, the rest from skip
     int cbq = 0, th = 0, tw = 0, tiles_x = 0, tiles_y = 0;   // dw tiling (forward kernel)
     int dw_n = 4;                                             // channels per work-item of the LDS-tiled depthwise kernels (8: bf16 plans, storage-typed LDS patches; fd_lane)
-    mutable int lds_rounding = 0;                             // fd_train_plan_lds_rounding: set by the launches of the last forward / backward
-    mutable int bwd_rows = 0;                                 // the LAST backward of this depthwise unit ran on a row-walking kernel (fd_dw5_bwd_rows / fd_dw3_bwd_rows)
     int bth = 0, btw = 0;                                     // output-space tile of the backward-weights kernel
-    int rows_th = 0;                                          // > 0: the forward runs on fd_dw3_rows_train with row strips of this height
-    int dw3_cl = 0, dw3_groups = 0, dw3_bh = 0;               // dw3_cl > 0: the forward runs on fd_dw3_rows_fwd (16-bit plans, 3x3 on a plain input): channel lanes per strip, strip groups per row, output rows per band
-    int dw5_groups = 0, dw5_bh = 0;                           // > 0: the forward runs on fd_dw5_rows_train (16-bit plans, 5x5 on up2 + skip): strip pairs per row, rows per band
+    // depthwise forward form: fd_dwconv_train (LDS-tiled) / fd_dw3_rows_train (register window) / fd_dw3_rows_fwd / fd_dw5_rows_train (16-bit plans: row-walking)
+    enum class DwFwd { TILED, REGWIN, ROWS3, ROWS5 } fwd = DwFwd::TILED;
+    int rows_th = 0;                                          // REGWIN: row-strip height
+    int rows_cl = 0, rows_groups = 0, rows_bh = 0;            // ROWS3 / ROWS5: channel lanes per strip (ROWS3), strip groups per row, output rows per band
+    int stemw_groups = 0, stemw_bh = 0;                       // > 0: the stem's backward weights run on fd_stem_wgrad_rows (16-bit plans): column groups per row, rows per band
+    // depthwise backward form (dw_bwd_plan, fd_train_impl.h): fd_dw5_bwd_rows / fd_dw3_bwd_rows / fd_dw3s2_bwd_rows / fd_dw3s2_dgrad_rows + fd_dw3_wgrad_rows /
+    // fd_dw_bwd1 / fd_dw_bwd / fd_dw_wgrad + fd_dw_dgrad
+    enum class DwBwd { ROWS5, ROWS3, ROWS3S2, REGWIN_S2, BWD1, PAIR, SEPARATE } bwd = DwBwd::SEPARATE;
+    int d_th = 0, d_tw = 0, d_tiles_x = 0, d_gx = 0;          // LDS-tiled backward data (BWD1 / PAIR / SEPARATE): input-space tile, tiles per row / per image
+    int w_tiles_x = 0, w_tpw = 0, w_gx = 0;                   // LDS-tiled backward weights: output-space tiles per row, tiles per workgroup, workgroups per image
+    int rb_groups = 0, rb_bh = 0, rb_wgs = 0, rb_cl = 0;      // row kernels: column groups per row, rows per band, workgroups per image and role, channel lanes (ROWS3)
+    int rw_th_d = 0, rw_th_w = 0;                             // REGWIN_S2: strip heights of fd_dw3s2_dgrad_rows / fd_dw3_wgrad_rows ...
+    dim3 rw_grid_d, rw_grid_w;                                // ... and their grids
+    size_t blds = 0, blds2 = 0;                               // dynamic LDS: BWD1 / PAIR (+ the in-kernel finalisation's coefficients); SEPARATE: fd_dw_dgrad / fd_dw_wgrad
+    long nblk_b = 0;                                          // backward-data workgroups (all images) that deal partials to the producer's backward statistics rows
     int stem_band = 0;                                        // floats of the stem kernels' input band in LDS
     int pstr = 0, bpstr = 0;                                  // LDS patch pitch (floats) of the forward / the backward depthwise kernels
     int chunk = 0;                                            // stem
@@ -70,10 +80,9 @@ struct fd_train_layer {
     int nblk = 0;                    // workgroups per channel of this unit's forward kernel that add a partial sum to its statistics rows
     int nr_cap = 1;                  // statistics rows reserved per direction (stat_nr of the unit's pixel count / 64)
     int nr_f = 1;                    // rows its forward kernel deals its partials to (stat_nr(nblk), <= nr_cap)
-    mutable int nr_b = 1;            // rows the backward kernel of its CONSUMER dealt the (sum G, sum G*xhat) partials to (set at that launch)
+    int nr_b = 1;                    // rows the backward kernel of its CONSUMER deals the (sum G, sum G*xhat) partials to (stat_nr of that kernel's nblk_b)
     size_t sf_off = 0, sb_off = 0;   // forward / backward statistics rows
-    bool bwd_fin = false;            // the unit's first backward kernel can finalise its BatchNorm backward (bwd_fin_candidate)
-    mutable int bwd_fin_rows = 0;    // > 0: it does so in this step (= nr_b; set when the consumer's backward kernels were launched)
+    int bwd_fin_rows = 0;            // > 0: the unit's first backward kernel finalises its BatchNorm backward from these nr_b rows (bwd_fin_candidate)
     bool fin_by_consumer = false;    // this unit's BatchNorm is finalised inside its consumer's forward kernel (no fd_bn_finalize_rows_f32 launch)
     size_t z_off = 0, z_elems = 0;   // raw output
     size_t st_off = 0;               // [4][C] table
@@ -150,13 +159,8 @@ inline size_t stat_rows_bytes(int nr, int C) { return ((size_t)nr * FD_STAT_BINS
 inline long long *stat_ptr(fd_train_plan *p, size_t off) { return reinterpret_cast<long long *>(p->ws + off); }
 // this unit's forward rows as its producer kernel sees them
 inline fd_stat_rows fwd_rows(fd_train_plan *p, const TLayer &L) { return fd_stat_rows{stat_ptr(p, L.sf_off), L.nr_f, stat_pitch(L.d.cout)}; }
-// unit u's backward rows as the backward-data kernel of its consumer (nblk workgroups per channel) sees them; remembers the row count for u's finalisation
-inline fd_stat_rows bwd_rows(fd_train_plan *p, int u, long nblk)
-{
-    const TLayer &U = p->layers[u];
-    U.nr_b = U.head ? U.nr_cap : std::min(U.nr_cap, stat_nr(nblk));      // (the head's single channel: every row is a line of its own -- all of them)
-    return fd_stat_rows{stat_ptr(p, U.sb_off), U.nr_b, stat_pitch(U.d.cout)};
-}
+// unit u's backward rows as the backward-data kernel of its consumer sees them
+inline fd_stat_rows bwd_rows(fd_train_plan *p, int u) { const TLayer &U = p->layers[u]; return fd_stat_rows{stat_ptr(p, U.sb_off), U.nr_b, stat_pitch(U.d.cout)}; }
 
 // calls fn(fd_int<4>) or -- 16-bit storage types only -- fn(fd_int<8>): the lane width (fd_lane) of the LDS-tiled depthwise kernels
 template <typename T, typename F> inline void fd_by_lane_width(int n, F &&fn)
@@ -167,61 +171,35 @@ template <typename T, typename F> inline void fd_by_lane_width(int n, F &&fn)
 // host mirror of fd_lds_patch_bytes (fd_kernels_train.h): bytes of an LDS patch image of npx pixels at pitch pstr in elements of `le` bytes
 inline size_t lds_patch_bytes(long npx, int pstr, int le) { return std::max(align_up((size_t)npx * pstr * le, 16), (size_t)8192); }
 
-// ---- which backward form a unit takes: decided at plan time (fd_train_plan_create) and replayed by the launches (fd_train_bwd_impl.h) ----
-// the paired depthwise launch has an instance for this unit's kernel size / stride / input composition / activations (dispatch_dw_bwd_pair)
-inline bool dw_bwd_has_pair(const fd_train_plan *p, int i)
+// ---- the depthwise backward ----
+template <int K_, int S_, int MODE_, int ACT1_, int ACT2_, int ADD_SG_> struct fd_dw_inst {
+    static constexpr int K = K_, S = S_, MODE = MODE_, ACT1 = ACT1_, ACT2 = ACT2_, ADD_SG = ADD_SG_;
+};
+// calls fn(fd_dw_inst<...>) with the instance of the single / paired / row-walking backward kernels for depthwise unit i's kernel size / stride / input
+// composition / activations (act2: the skip tensor's); false: none (an unusual combination -- sibling / custom plans: the two separate kernels cover it)
+template <typename F> inline bool fd_by_dw_instance(const fd_train_plan *p, int i, F &&fn)
 {
     const TLayer &L = p->layers[i];
     const TLayer &P = p->layers[L.d.src];
     const int a1 = P.d.act, a2 = L.d.skip >= 0 ? p->layers[L.d.skip].d.act : FD_ACT_RELU6;
     const bool add = P.skip_consumer >= 0 && L.mode == 0;
-    const int key = L.d.ksize * 100 + L.d.stride * 10 + L.mode;
-    if (a1 == FD_ACT_RELU6 && !add && (key == 310 || key == 320 || key == 510)) return true;
-    if (a1 == FD_ACT_RELU6 && add && key == 320) return true;
-    if (a1 == FD_ACT_RELU && key == 511) return true;
-    if (a1 == FD_ACT_RELU && a2 == FD_ACT_RELU6 && (key == 512 || key == 513)) return true;
+    switch (L.d.ksize * 100 + L.d.stride * 10 + L.mode) {
+    case 310: if (a1 != FD_ACT_RELU6 || add) return false; fn(fd_dw_inst<3, 1, 0, FD_ACT_RELU6_, FD_ACT_RELU6_, 0>{}); return true;
+    case 320:
+        if (a1 != FD_ACT_RELU6) return false;
+        if (add) fn(fd_dw_inst<3, 2, 0, FD_ACT_RELU6_, FD_ACT_RELU6_, 1>{}); else fn(fd_dw_inst<3, 2, 0, FD_ACT_RELU6_, FD_ACT_RELU6_, 0>{});
+        return true;
+    case 510: if (a1 != FD_ACT_RELU6 || add) return false; fn(fd_dw_inst<5, 1, 0, FD_ACT_RELU6_, FD_ACT_RELU6_, 0>{}); return true;
+    case 511: if (a1 != FD_ACT_RELU) return false; fn(fd_dw_inst<5, 1, 1, FD_ACT_RELU_, FD_ACT_RELU6_, 0>{}); return true;
+    case 512: if (a1 != FD_ACT_RELU || a2 != FD_ACT_RELU6) return false; fn(fd_dw_inst<5, 1, 2, FD_ACT_RELU_, FD_ACT_RELU6_, 0>{}); return true;
+    case 513: if (a1 != FD_ACT_RELU || a2 != FD_ACT_RELU6) return false; fn(fd_dw_inst<5, 1, 3, FD_ACT_RELU_, FD_ACT_RELU6_, 0>{}); return true;
+    }
     return false;
 }
-// the stride-2 3x3 units of the large maps run their backward on the two register-window kernels (launch_dw_bwd_pair)
-inline bool dw_bwd_on_rows(const fd_train_plan *p, const TLayer &L)
+// the unit's backward runs on a row-walking kernel of fd_kernels_dw5p_bwd.h
+inline bool bwd_on_row_kernel(const TLayer &L)
 {
-    const int cgn = L.d.cin / 4;
-    const bool rows_ok = L.d.ksize == 3 && L.d.stride == 2 && L.mode == 0 && L.d.cin % 4 == 0 && cgn >= 8 && cgn <= 64 && (cgn & (cgn - 1)) == 0 &&
-                         (((long)L.out_h * L.out_w >= 28 * 28 && p->esz == 2) || (p->tune & FD_TUNE_DW_FORCE_ROWS));
-    return rows_ok && !(p->tune & (FD_TUNE_DW_NO_ROWS | FD_TUNE_DW_BWD_PAIR | FD_TUNE_DW_BWD1));
+    return L.d.op == FD_OP_DW && (L.bwd == TLayer::DwBwd::ROWS5 || L.bwd == TLayer::DwBwd::ROWS3 || L.bwd == TLayer::DwBwd::ROWS3S2);
 }
-#ifndef FD_DW_ROWS_FIN
-#define FD_DW_ROWS_FIN 1               // the row-walking backward kernels finalise their unit's BatchNorm backward in the prologue (0: the separate launch; A/B switch)
-#endif
-#ifndef FD_DW3_ROWS_MIN_PIXELS
-#define FD_DW3_ROWS_MIN_PIXELS 0      // maps below this many pixels keep the paired LDS-tiled launch (tools/build_variant.py A/B switch)
-#endif
-// the unit's backward runs on a row-walking kernel of fd_kernels_dw5p_bwd.h (the launch-time conditions of launch_dw_bwd_pair, fd_train_bwd_impl.h)
-inline bool dw_bwd_row_kernel(const fd_train_plan *p, int i)
-{
-    const TLayer &L = p->layers[i];
-    if (p->esz != 2 || L.d.op != FD_OP_DW || L.d.cin % 8 || (double)L.in_h * L.in_w * L.d.cin * 2.0 >= 2147483648.0 || (p->flags & FD_PLAN_NO_BWD_PAIRING) || !dw_bwd_has_pair(p, i)) return false;
-    if (p->tune & (FD_TUNE_NO_DW5_ROWS | FD_TUNE_DW_BWD1 | FD_TUNE_DW_BWD_PAIR)) return false;
-    const bool add = p->layers[L.d.src].skip_consumer >= 0 && L.mode == 0;
-    if (L.d.ksize == 5 && L.d.stride == 1 && L.mode == 2) return L.in_w % 4 == 0 && L.in_h % 2 == 0;
-    if (p->tune & FD_TUNE_FORCE_DW_H8) return false;
-    if (L.d.ksize == 3 && L.d.stride == 1 && L.mode == 0) return !add && (long)L.in_h * L.in_w >= FD_DW3_ROWS_MIN_PIXELS;
-    if (L.d.ksize == 3 && L.d.stride == 2 && L.mode == 0) return !(p->tune & (FD_TUNE_DW_FORCE_ROWS | FD_TUNE_DW_NO_ROWS));
-    return false;
-}
-// plan-time half of TLayer::bwd_fin: the unit's first backward kernel CAN finalise its BatchNorm backward (the LDS-tiled depthwise launches, the
-// apply pass of the 16-bit pointwise units); whether it does is decided per step by the number of partial rows its consumer left (finalize_or_defer)
-inline bool bwd_fin_candidate(const fd_train_plan *p, int i)
-{
-    const TLayer &L = p->layers[i];
-    if ((p->tune & FD_TUNE_NO_CONSUMER_FINALIZE) || L.head || L.d.src < 0) return false;
-    if (L.d.op == FD_OP_PW) return p->esz == 2;           // (16-bit plans: the apply pass fd_bn_bwd_apply_fin_h16; any row count now that the rows are few)
-    // (depthwise units: built and measured in round 4 with up to 128 fp32 partial rows, off by default -- bf16 step: the 10 launches it removed were 43 us, the
-    // paired kernels got 40 us slower (163 VGPRs + 36 bytes of scratch in the 3x3 instance); fp32 step +26 us.  FD_TUNE_DW_BWD_FINALIZE turns it on: tests, A/B)
-    if (L.d.op == FD_OP_DW && FD_DW_ROWS_FIN && dw_bwd_row_kernel(p, i)) return true;     // (round 6: the row-walking kernels derive the coefficients in their prologue -- no registers carried through the walk)
-    if (L.d.op == FD_OP_DW) return (p->tune & FD_TUNE_DW_BWD_FINALIZE) && !(p->flags & FD_PLAN_NO_BWD_PAIRING) && dw_bwd_has_pair(p, i) && !dw_bwd_on_rows(p, L);
-    return false;
-}
-
 
 }  // namespace

@@ -44,17 +44,17 @@ extern "C" {
 /* the mask applies to the next plan this thread creates (then resets to 0); unknown bits are rejected by that creation */
 void fd_tuning_next(uint32_t mask);
 /* Test hook of the layer-local train parity (tests/harness.py: the fp64 single-unit reference rounds exactly where the kernels round): which
- * kernels of depthwise unit `layer` kept their LDS patches in the 16-bit storage type during the LAST forward / backward of this plan --
- * bit 0: the forward kernel rounded its (activated, upsampled, skip-added) conv input; bit 1: the backward kernels rounded dz and the
- * re-created conv input; bit 2 / bit 3: the forward / the backward-data kernel rounded its taps as well (fd_dw5_rows_train / fd_dw5_bwd_rows).  0 for fp32 plans, the 4-channel form and the
+ * kernels of depthwise unit `layer` keep their LDS patches in the 16-bit storage type in the forms the plan chose for it (valid right after creation) --
+ * bit 0: the forward kernel rounds its (activated, upsampled, skip-added) conv input; bit 1: the backward kernels round dz and the
+ * re-created conv input; bit 2 / bit 3: the forward / the backward-data kernel rounds its taps as well (fd_dw5_rows_train / fd_dw5_bwd_rows).  0 for fp32 plans, the 4-channel form and the
  * register-window kernels.  -1: bad arguments. */
 struct fd_train_plan;
 int fd_train_plan_lds_rounding(const struct fd_train_plan *plan, int32_t layer);
 /* Test hook: which of the selectable forms unit `layer` of a train plan runs on -- bit 0: its forward pointwise GEMM is fd_pw_gemm16_f32 in train mode
  * (fp32 plans, one round of workgroups); bit 1: its BatchNorm statistics are finalised inside the consuming depthwise kernel (fd_bn_finalize_block);
- * bit 2: in the LAST backward its BatchNorm backward was finalised inside its own first backward kernel (fd_bn_bwd_apply_fin_h16 /
- * fd_bn_bwd_finalize_block); bit 3: its LAST backward ran on a row-walking depthwise kernel (fd_dw5_bwd_rows / fd_dw3_bwd_rows / fd_dw3s2_bwd_rows); bit 4: its forward runs on
- * fd_dw5_rows_train; bit 5: on fd_dw3_rows_fwd.  -1: bad arguments. */
+ * bit 2: in the plan its BatchNorm backward is finalised inside its own first backward kernel (fd_bn_bwd_apply_fin_h16 /
+ * fd_bn_bwd_finalize_block); bit 3: in the plan its backward runs on a row-walking depthwise kernel (fd_dw5_bwd_rows / fd_dw3_bwd_rows / fd_dw3s2_bwd_rows); bit 4: its forward runs on
+ * fd_dw5_rows_train; bit 5: on fd_dw3_rows_fwd.  All of it is chosen at plan creation (valid right after it).  -1: bad arguments. */
 int fd_train_plan_unit_kernels(const struct fd_train_plan *plan, int32_t layer);
 /* Measurement hook (tools/gpu_round.sh, bench.py with FD_BENCH_FORCE_DIST=2): fd_train_backward_allreduce runs everything -- bucket ranges, event
  * hand-over to the communicator's stream, casts, the wait of the compute stream -- EXCEPT the ncclAllReduce calls.  On one rank this separates the

@@ -288,21 +288,24 @@ def local_train_parity(kind, model, x, target, device, dtype=torch.float32, flag
     rnd = (lambda t: t.float().to(dtype).double()) if h16 else (lambda t: t)
     run0 = [(l.bn.running_mean.detach().double().clone(), l.bn.running_var.detach().double().clone()) for l in layers_of(model)]
     tp = CTrainPlan(kind, model, x.to(device), keep=True, dtype=dtype, flags=flags)
+    L, n = tp.layers, tp.n
+    # which depthwise kernels keep their LDS patches in the 16-bit storage type (private test hook, csrc/fd_tuning.h): bit 0 forward, bit 1 backward,
+    # bit 2 / bit 3: the forward / the backward-data kernel also rounds its taps (fd_dw5_rows_train / fd_dw5_bwd_rows); and which forms each unit runs on.
+    # Both are the plan's: they answer right after creation and do not change with a step.
+    tp.lib.fd_train_plan_lds_rounding.restype = ctypes.c_int
+    tp.lib.fd_train_plan_lds_rounding.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+    tp.lib.fd_train_plan_unit_kernels.restype = ctypes.c_int
+    tp.lib.fd_train_plan_unit_kernels.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+    hooks = lambda: ([max(tp.lib.fd_train_plan_lds_rounding(tp.h, i), 0) for i in range(n)], [max(tp.lib.fd_train_plan_unit_kernels(tp.h, i), 0) for i in range(n)])
+    planned = hooks()
     y = tp.forward(x.to(device)).cpu()
     dpred = torch.sign(y - target) / y.numel()
     grads = tp.backward(dpred)
-    L, n = tp.layers, tp.n
     Z = [tp.tensor(i, 0).double() for i in range(n)]
     ST = [tp.tensor(i, 2).double()[0, :, :, 0].t() for i in range(n)]
     G = [tp.tensor(i, 1).double() for i in range(n)]
-    # which depthwise kernels kept their LDS patches in the 16-bit storage type (private test hook, csrc/fd_tuning.h): bit 0 forward, bit 1 backward,
-    # bit 2 / bit 3: the forward / the backward-data kernel also rounds its taps (fd_dw5_rows_train / fd_dw5_bwd_rows)
-    tp.lib.fd_train_plan_lds_rounding.restype = ctypes.c_int
-    tp.lib.fd_train_plan_lds_rounding.argtypes = [ctypes.c_void_p, ctypes.c_int32]
-    lds_round = [max(tp.lib.fd_train_plan_lds_rounding(tp.h, i), 0) for i in range(n)]
-    tp.lib.fd_train_plan_unit_kernels.restype = ctypes.c_int
-    tp.lib.fd_train_plan_unit_kernels.argtypes = [ctypes.c_void_p, ctypes.c_int32]
-    forms = [max(tp.lib.fd_train_plan_unit_kernels(tp.h, i), 0) for i in range(n)]
+    lds_round, forms = hooks()
+    assert (lds_round, forms) == planned, "the plan's forms changed with a step: %s -> %s" % (planned, (lds_round, forms))
     rep_info = {"dw_units_with_16bit_lds_patches": sum(1 for v in lds_round if (v & 3) and not (v & (4 | 8))), "dw_units_on_dw5_bwd_rows": sum(1 for v in lds_round if v & 8), "dw_units_on_dw5_rows_train": sum(1 for v in lds_round if v & 4), "pw_units_on_gemm16": sum(1 for v in forms if v & 1),
                 "dw_units_backward_on_row_kernels": sum(1 for v in forms if v & 8), "dw_units_on_dw3_rows_fwd": sum(1 for v in forms if v & 32), "units_finalised_by_consumer": sum(1 for v in forms if v & 2), "units_finalising_their_own_backward": sum(1 for v in forms if v & 4)}
     consumers = {}

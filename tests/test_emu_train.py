@@ -247,6 +247,16 @@ def test_train_plan_dtype_rules():
     harness.CTrainPlan("emu", odd, x, dtype=torch.float32).close()    # multiples of 4 are fine in fp32
     with pytest.raises(capi.FastDepthError):
         harness.CTrainPlan("emu", odd, x, dtype=torch.bfloat16)       # 16-byte bf16 chunks need multiples of 8
+    import models
+    with pytest.raises(capi.FastDepthError):                          # skip-free, 64 x 40: conv6.0 would see a 5-wide map
+        harness.CTrainPlan("emu", models.MobileNet("nnconv5dw", (64, 40), pretrained=False), torch.rand(1, 3, 64, 40))
+    # descriptors from the C ABI: a stride-2 unit on the 2 x 3 map (mobilenet.13.0) and one more upsampling decoder unit -- the head's height comes out
+    # right (64), its width does not (64 for a 96-wide input)
+    lib = harness.get_lib("emu")
+    descs = (capi.LayerDesc * 38)(*[l.desc for l in harness.layers_of(models.MobileNet("nnconv5dw", (64, 96), pretrained=False))])
+    descs[25].stride, descs[27].upsample = 2, 1
+    h = ctypes.c_void_p()
+    assert capi.create_plan(lib, True, descs, 38, 1, 64, 96, capi.DTYPE_OF[torch.float32], 0, ctypes.byref(h)) != 0
 
 
 def test_emulated_val_transform_gather():
