@@ -709,6 +709,97 @@ int fd_val_transform(const void *rgb_u8, const float *depth, int32_t n, int32_t 
     return check_launch("fd_val_transform_u8");
 }
 
+// scratch of fd_train_transform: [n] frame headers | y1[FD_AUG_MAX_H1] | x1[FD_AUG_MAX_W1] | ytab[n][out_h] | xtab[n][out_w] | stash[n][out_h * out_w] (uint32)
+namespace {
+struct AugScratch { size_t frames, y1, x1, ytab, xtab, stash, total; };
+AugScratch aug_scratch(int32_t n, int32_t oh, int32_t ow)
+{
+    AugScratch a;
+    a.frames = 0;
+    a.y1 = align_up((size_t)n * sizeof(fd_aug_frame), 256);
+    a.x1 = a.y1 + (size_t)FD_AUG_MAX_H1 * sizeof(int);
+    a.ytab = a.x1 + (size_t)FD_AUG_MAX_W1 * sizeof(int);
+    a.xtab = align_up(a.ytab + (size_t)n * oh * sizeof(int), 256);
+    a.stash = align_up(a.xtab + (size_t)n * ow * sizeof(int), 256);
+    a.total = a.stash + (size_t)n * oh * ow * sizeof(unsigned);
+    return a;
+}
+// Can the host read the records where they are?  (Page-locked host memory the device reads in place; everything is host memory in the emulator.)
+// -1: the device cannot read the pointer at all (pageable host memory).
+int aug_params_host_readable(const void *p)
+{
+#ifdef FD_EMU
+    (void)p;
+    return 1;
+#else
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    if (a.type == hipMemoryTypeHost) return 1;
+    return (a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged) ? 0 : -1;
+#endif
+}
+}  // namespace
+
+size_t fd_train_transform_scratch_bytes(int32_t n, int32_t out_h, int32_t out_w)
+{
+    if (n <= 0 || out_h <= 0 || out_w <= 0) return 0;
+    return aug_scratch(n, out_h, out_w).total;
+}
+
+int fd_train_transform(const void *rgb_u8, const float *depth, int32_t n, int32_t height, int32_t width, int32_t out_h, int32_t out_w,
+                       const fd_aug_params *params_device, float *x_out, float *depth_out, void *scratch, void *stream)
+{
+    if (!rgb_u8 || !params_device || !x_out || !scratch || n <= 0 || height <= 0 || width <= 0 || out_h <= 0 || out_w <= 0)
+        return fail(FD_ERR_INVALID, "fd_train_transform: null/empty argument");
+    if ((depth == nullptr) != (depth_out == nullptr)) return fail(FD_ERR_INVALID, "fd_train_transform: depth and depth_out go together");
+    if ((long)out_h * out_w > (1L << 28) || (long)height * width > (1L << 28)) return fail(FD_ERR_INVALID, "fd_train_transform: frame of more than 2^28 pixels");
+    if (reinterpret_cast<uintptr_t>(scratch) & 127) return fail(FD_ERR_INVALID, "fd_train_transform: scratch must be 128-byte aligned");
+    // Resize(250.0 / iheight) with a float: size = (array(im.size) * f).astype(int)   (reference nyu.py:34, scipy.misc.imresize)
+    const double f = 250.0 / height;
+    const int h1 = (int)(height * f), w1 = (int)(width * f);
+    // Too small: no scale that fd_aug_record_check admits (s <= FD_AUG_MAX_SCALE) makes the resized image cover the crop.
+    if ((int)(h1 * FD_AUG_MAX_SCALE) < FD_AUG_CROP_H || (int)(w1 * FD_AUG_MAX_SCALE) < FD_AUG_CROP_W)
+        return fail(FD_ERR_INVALID, "fd_train_transform: a %d x %d frame is too small for the %d x %d crop (it resizes to %d x %d, and to %g times that at most)",
+                    height, width, FD_AUG_CROP_H, FD_AUG_CROP_W, h1, w1, (double)FD_AUG_MAX_SCALE);
+    // h1 <= 250 by construction; the first resize's column table in scratch holds FD_AUG_MAX_W1 entries.
+    if (h1 > FD_AUG_MAX_H1 || w1 > FD_AUG_MAX_W1)
+        return fail(FD_ERR_INVALID, "fd_train_transform: a %d x %d frame resizes to %d x %d, beyond the %d x %d the tables are planned for", height, width, h1, w1,
+                    FD_AUG_MAX_H1, FD_AUG_MAX_W1);
+    // The records live where the device reads them.  Where the host can read them too they are checked here; in plain device memory the table step
+    // applies the same rule (fd_aug_record_check) and a refused frame comes out as zeros -- no read-back, nothing here synchronises.
+    const int readable = aug_params_host_readable(params_device);
+    if (readable < 0) return fail(FD_ERR_INVALID, "fd_train_transform: params_device is not memory the device can read");
+    if (readable > 0)
+        for (int i = 0; i < n; ++i) {
+            const fd_aug_params &p = params_device[i];
+            switch (fd_aug_record_check(p, h1, w1)) {
+            case 1: return fail(FD_ERR_INVALID, "fd_train_transform: frame %d: order (%d, %d, %d) is not a permutation of {0, 1, 2}", i, p.order[0], p.order[1], p.order[2]);
+            case 2: return fail(FD_ERR_INVALID, "fd_train_transform: frame %d: s = %g is not in (0, %g]", i, p.s, (double)FD_AUG_MAX_SCALE);
+            case 3: return fail(FD_ERR_INVALID, "fd_train_transform: frame %d: s = %g resizes %d x %d to %d x %d, smaller than the %d x %d crop", i, p.s, h1, w1,
+                                (int)(h1 * p.s), (int)(w1 * p.s), FD_AUG_CROP_H, FD_AUG_CROP_W);
+            case 4: return fail(FD_ERR_INVALID, "fd_train_transform: frame %d: a colour factor (%g, %g, %g) or the angle (%g) is not finite", i, (double)p.brightness, (double)p.contrast,
+                                (double)p.saturation, p.angle);
+            default: break;
+            }
+        }
+    const AugScratch a = aug_scratch(n, out_h, out_w);
+    char *base = static_cast<char *>(scratch);
+    fd_aug_frame *frames = reinterpret_cast<fd_aug_frame *>(base + a.frames);
+    int *y1 = reinterpret_cast<int *>(base + a.y1), *x1 = reinterpret_cast<int *>(base + a.x1);
+    int *ytab = reinterpret_cast<int *>(base + a.ytab), *xtab = reinterpret_cast<int *>(base + a.xtab);
+    unsigned *stash = reinterpret_cast<unsigned *>(base + a.stash);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const long px = (long)out_h * out_w;
+    FD_LAUNCH(fd_aug_tables, dim3((unsigned)n + 1), dim3(256), 0, s, params_device, frames, y1, x1, ytab, xtab, n, height, width, h1, w1, out_h, out_w);
+    int rc = check_launch("fd_aug_tables");
+    if (rc) return rc;
+    FD_LAUNCH(fd_aug_gather, dim3((unsigned)ceil_div(px, 256L * FD_AUG_PIX_PER_ITEM), (unsigned)n), dim3(256), 0, s, static_cast<const unsigned char *>(rgb_u8), depth,
+              frames, y1, x1, ytab, xtab, stash, depth_out, height, width, h1, w1, out_h, out_w);
+    if ((rc = check_launch("fd_aug_gather"))) return rc;
+    FD_LAUNCH(fd_aug_apply, dim3((unsigned)ceil_div(px, 1024), (unsigned)n), dim3(256), 0, s, frames, stash, x_out, out_h, out_w);
+    return check_launch("fd_aug_apply");
+}
+
 int fd_cast_gradients(const void *src, void *dst, int64_t numel, int32_t to_bf16, void *stream)
 {
     if (!src || !dst || numel <= 0) return fail(FD_ERR_INVALID, "fd_cast_gradients: null/empty argument");
