@@ -6,6 +6,7 @@
 #pragma once
 #include "fd_device.h"
 #include "../../include/fastdepth_hip.h"
+#include "fd_viridis.h"
 
 static __global__ void __launch_bounds__(256)
 fd_val_transform_u8(const unsigned char *__restrict__ rgb, const float *__restrict__ depth, const int *__restrict__ ymap,
@@ -221,6 +222,143 @@ fd_aug_apply(const fd_aug_frame *__restrict__ frames, const unsigned *__restrict
         fd_aug_color_op(o2, a2, m, r, g, b);
         float *o = x + (long)f * 3 * px + i;
         o[0] = unit[r]; o[px] = unit[g]; o[2L * px] = unit[b];
+    }
+}
+
+// ---- comparison rows (reference utils.py:37-74 colored_depthmap / merge_into_row / merge_into_row_with_gt, deploy/data/visualize.py:22-31): per frame
+// `colour frame | depth map ... ` as uint8 RGB, the depth panels viridis-coloured over the frame's joint range.  The reference goes through
+// .cpu().numpy(), matplotlib's Colormap.__call__ (float64 over [H, W, 4]) and np.hstack; the arithmetic that decides a byte is small and fixed:
+//     rel = (d - d_min) / (d_max - d_min), t = rel * 256      float32, each operation rounded on its own (no reciprocal, no contraction)
+//     NaN -> black; t < 0 -> entry 0; t >= 256 -> entry 255 (t == 256 is matplotlib's "1.0 is inside"); otherwise entry int(t)
+//     byte = uint8(255 * viridis[entry][c])                   the table of fd_viridis.h
+//     colour frame: uint8(255.0f * x), the product in float32, truncated
+// Two launches.  fd_viz_range (skipped when the caller gives the ranges): every workgroup reduces its share of a frame's maps with the NaN-propagating
+// IEEE minimum / maximum and stores ONE (min, max) partial in its own scratch slot -- plain stores, nothing to zero, no atomics.  fd_viz_paint finishes a
+// frame's partials in its prologue (minimum / maximum are exact, commutative and associative, NaN included: any combination order gives the same
+// bits), as the train kernels finish the BatchNorm tables, and paints.
+#define FD_VIZ_MAX_PARTS 32          /* workgroups of fd_viz_range per frame, at most: wave 0 of fd_viz_paint finishes them in one shuffle tree */
+#define FD_VIZ_PART_ELEMS 4096       /* elements a workgroup of fd_viz_range reduces before a further one is worth its launch */
+#define FD_VIZ_STORE4 1              /* fd_viz_paint: three dword stores per work-item (w % 4 == 0, pitch % 4 == 0, canvas 4-byte aligned) */
+#define FD_VIZ_LOAD4 2               /* 16-byte loads (w % 4 == 0 and every input plane 16-byte aligned) */
+static_assert(FD_VIZ_MAX_PARTS <= 64, "one wave of fd_viz_paint finishes a frame's partials");
+
+__device__ __forceinline__ float fd_viz_min(float a, float b) { return __builtin_elementwise_minimum(a, b); }     // NaN if either is NaN (np.min)
+__device__ __forceinline__ float fd_viz_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+// all 64 lanes of the calling wave take part
+__device__ __forceinline__ void fd_viz_wave_minmax(float &lo, float &hi)
+{
+    for (int m = 32; m >= 1; m >>= 1) { lo = fd_viz_min(lo, __shfl_xor(lo, m)); hi = fd_viz_max(hi, __shfl_xor(hi, m)); }
+}
+
+// grid (n, parts <= FD_VIZ_MAX_PARTS) -- the frame in x, which has no 65535 limit: partials[f][FD_VIZ_MAX_PARTS][2]; workgroup (g, f) writes slot g of frame f.  px = h * w.
+static __global__ void __launch_bounds__(256)
+fd_viz_range(const float *__restrict__ m0, const float *__restrict__ m1, const float *__restrict__ m2, float *__restrict__ partials, long px, int load4)
+{
+    __shared__ float part[2][4];
+    const int f = (int)blockIdx.x, g = (int)blockIdx.y, tid = (int)threadIdx.x;
+    const long first = (long)g * 256 + tid, step = (long)gridDim.y * 256;
+    float lo = __builtin_huge_valf(), hi = -__builtin_huge_valf();
+    for (int m = 0; m < 3; ++m) {
+        const float *p = m == 0 ? m0 : (m == 1 ? m1 : m2);
+        if (!p) break;
+        p += (long)f * px;
+        if (load4) {
+            for (long q = first; q < (px >> 2); q += step) {
+                const fd_f32x4 v = fd_ld4(p + 4 * q);
+                lo = fd_viz_min(fd_viz_min(lo, v.x), fd_viz_min(fd_viz_min(v.y, v.z), v.w));
+                hi = fd_viz_max(fd_viz_max(hi, v.x), fd_viz_max(fd_viz_max(v.y, v.z), v.w));
+            }
+        } else {
+            for (long i = first; i < px; i += step) { const float v = p[i]; lo = fd_viz_min(lo, v); hi = fd_viz_max(hi, v); }
+        }
+    }
+    fd_viz_wave_minmax(lo, hi);
+    if ((tid & 63) == 0) { part[0][tid >> 6] = lo; part[1][tid >> 6] = hi; }
+    __syncthreads();
+    if (tid == 0) {
+        float *o = partials + ((long)f * FD_VIZ_MAX_PARTS + g) * 2;
+        o[0] = fd_viz_min(fd_viz_min(part[0][0], part[0][1]), fd_viz_min(part[0][2], part[0][3]));
+        o[1] = fd_viz_max(fd_viz_max(part[1][0], part[1][1]), fd_viz_max(part[1][2], part[1][3]));
+    }
+}
+
+// one depth value -> its packed colour (r | g << 8 | b << 16)
+__device__ __forceinline__ unsigned fd_viz_colour(const unsigned *lut, float d, float d_min, float span)
+{
+#pragma clang fp contract(off)
+    const float rel = (d - d_min) / span;            // an IEEE division, as NumPy's
+    const float t = rel * 256.0f;
+    if (t != t) return 0u;                           // matplotlib's "bad": (0, 0, 0)
+    return lut[t < 0.0f ? 0 : (t >= 255.0f ? 255 : (int)t)];      // under; [255, 256) truncates to 255, t == 256 and over are 255 too
+}
+// uint8(double(255.0f * x)): truncated toward zero; saturates outside [0, 256 / 255), NaN -> 0 (the reference's cast is platform-defined there)
+__device__ __forceinline__ unsigned fd_viz_u8(float x)
+{
+    const float v = 255.0f * x;
+    return !(v > 0.0f) ? 0u : (v >= 255.0f ? 255u : (unsigned)(int)v);
+}
+
+// grid (n, gy).  A work-item paints 4 consecutive pixels of one panel row (fewer at the end of a row whose width is no multiple of 4); consecutive
+// work-items follow a canvas row through its panels, so a wave's stores are one contiguous run of 768 bytes.
+static __global__ void __launch_bounds__(256)
+fd_viz_paint(const float *__restrict__ x, const float *__restrict__ m0, const float *__restrict__ m1, const float *__restrict__ m2,
+             const float *__restrict__ range, const float *__restrict__ partials, int parts, unsigned char *__restrict__ canvas, long pitch,
+             int h, int w, int k, int flags)
+{
+    __shared__ unsigned lut[256];
+    __shared__ float bounds[2];
+    const int f = (int)blockIdx.x, tid = (int)threadIdx.x;
+    lut[tid] = (unsigned)fd_viridis_u8[tid][0] | ((unsigned)fd_viridis_u8[tid][1] << 8) | ((unsigned)fd_viridis_u8[tid][2] << 16);
+    if (range) {
+        if (tid < 2) bounds[tid] = range[2L * f + tid];
+    } else if (tid < 64) {                            // wave 0 finishes the frame's partials
+        const float *p = partials + ((long)f * FD_VIZ_MAX_PARTS + tid) * 2;
+        float lo = tid < parts ? p[0] : __builtin_huge_valf(), hi = tid < parts ? p[1] : -__builtin_huge_valf();
+        fd_viz_wave_minmax(lo, hi);
+        if (tid == 0) { bounds[0] = lo; bounds[1] = hi; }
+    }
+    __syncthreads();
+    const float d_min = bounds[0], span = bounds[1] - bounds[0];
+    const int panels = k + (x ? 1 : 0), wq = (w + 3) >> 2;
+    const long px = (long)h * w, items = (long)h * panels * wq;
+    for (long it = (long)blockIdx.y * 256 + tid; it < items; it += (long)gridDim.y * 256) {
+        const long rp = it / wq, y = rp / panels;
+        const int q = (int)(it - rp * wq), j = (int)(rp - y * panels), x0 = q * 4, cnt = w - x0 < 4 ? w - x0 : 4;
+        const int mi = x ? j - 1 : j;                 // -1: the colour frame
+        const long at = y * w + x0;
+        unsigned c[4] = {0u, 0u, 0u, 0u};
+        if (mi < 0) {
+            const float *p = x + (long)f * 3 * px + at;
+            if (flags & FD_VIZ_LOAD4) {
+                const fd_f32x4 r = fd_ld4(p), g = fd_ld4(p + px), b = fd_ld4(p + 2 * px);
+                c[0] = fd_viz_u8(r.x) | (fd_viz_u8(g.x) << 8) | (fd_viz_u8(b.x) << 16);
+                c[1] = fd_viz_u8(r.y) | (fd_viz_u8(g.y) << 8) | (fd_viz_u8(b.y) << 16);
+                c[2] = fd_viz_u8(r.z) | (fd_viz_u8(g.z) << 8) | (fd_viz_u8(b.z) << 16);
+                c[3] = fd_viz_u8(r.w) | (fd_viz_u8(g.w) << 8) | (fd_viz_u8(b.w) << 16);
+            } else {
+                for (int e = 0; e < cnt; ++e) c[e] = fd_viz_u8(p[e]) | (fd_viz_u8(p[px + e]) << 8) | (fd_viz_u8(p[2 * px + e]) << 16);
+            }
+        } else {
+            const float *p = (mi == 0 ? m0 : (mi == 1 ? m1 : m2)) + (long)f * px + at;
+            if (flags & FD_VIZ_LOAD4) {
+                const fd_f32x4 d = fd_ld4(p);
+                c[0] = fd_viz_colour(lut, d.x, d_min, span); c[1] = fd_viz_colour(lut, d.y, d_min, span);
+                c[2] = fd_viz_colour(lut, d.z, d_min, span); c[3] = fd_viz_colour(lut, d.w, d_min, span);
+            } else {
+                for (int e = 0; e < cnt; ++e) c[e] = fd_viz_colour(lut, p[e], d_min, span);
+            }
+        }
+        unsigned char *o = canvas + ((long)f * h + y) * pitch + ((long)j * w + x0) * 3;
+        if (flags & FD_VIZ_STORE4) {                  // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
+            unsigned *o4 = reinterpret_cast<unsigned *>(o);
+            o4[0] = c[0] | (c[1] << 24);
+            o4[1] = (c[1] >> 8) | (c[2] << 16);
+            o4[2] = (c[2] >> 16) | (c[3] << 8);
+        } else {
+            for (int e = 0; e < cnt; ++e) {
+                o[3 * e] = (unsigned char)(c[e] & 255u); o[3 * e + 1] = (unsigned char)((c[e] >> 8) & 255u); o[3 * e + 2] = (unsigned char)(c[e] >> 16);
+            }
+        }
     }
 }
 

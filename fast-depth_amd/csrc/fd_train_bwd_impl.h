@@ -800,6 +800,49 @@ int fd_train_transform(const void *rgb_u8, const float *depth, int32_t n, int32_
     return check_launch("fd_aug_apply");
 }
 
+// scratch of fd_depth_rows: float [n][FD_VIZ_MAX_PARTS][2], the (min, max) partials of fd_viz_range; every slot that is read has been written by this call
+size_t fd_depth_rows_scratch_bytes(int32_t n)
+{
+    if (n <= 0) return 0;
+    return (size_t)n * FD_VIZ_MAX_PARTS * 2 * sizeof(float);
+}
+
+int fd_depth_rows(const float *x_nchw, const float *map0, const float *map1, const float *map2, int32_t n, int32_t h, int32_t w, const float *range_device,
+                  uint8_t *canvas, int64_t pitch_bytes, void *scratch, void *stream)
+{
+    if (n <= 0 || h <= 0 || w <= 0) return fail(FD_ERR_INVALID, "fd_depth_rows: n, h and w must be positive (got %d, %d, %d)", n, h, w);
+    if (!map0) return fail(FD_ERR_INVALID, "fd_depth_rows: map0 is required");
+    if (!map1 && map2) return fail(FD_ERR_INVALID, "fd_depth_rows: map2 given without map1 (the maps are map0, map1, map2 in order)");
+    if (!canvas) return fail(FD_ERR_INVALID, "fd_depth_rows: canvas is NULL");
+    const int k = 1 + (map1 ? 1 : 0) + (map2 ? 1 : 0), panels = k + (x_nchw ? 1 : 0);
+    const int64_t row = (int64_t)panels * w * 3;
+    if (pitch_bytes < row)
+        return fail(FD_ERR_INVALID, "fd_depth_rows: pitch_bytes = %lld is smaller than a row of %d panels of %d pixels (%lld bytes)", (long long)pitch_bytes, panels, w,
+                    (long long)row);
+    if (!range_device && !scratch) return fail(FD_ERR_INVALID, "fd_depth_rows: scratch is NULL and no range_device is given (fd_depth_rows_scratch_bytes(n) bytes)");
+    if (reinterpret_cast<uintptr_t>(range_device) & 3 || reinterpret_cast<uintptr_t>(scratch) & 3)
+        return fail(FD_ERR_INVALID, "fd_depth_rows: range_device and scratch must be 4-byte aligned");
+    const long px = (long)h * w;
+    auto al = [](const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
+    int flags = 0;
+    if (w % 4 == 0 && pitch_bytes % 4 == 0 && al(canvas, 4)) flags |= FD_VIZ_STORE4;
+    if (w % 4 == 0 && al(x_nchw, 16) && al(map0, 16) && al(map1, 16) && al(map2, 16)) flags |= FD_VIZ_LOAD4;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float *partials = static_cast<float *>(scratch);
+    int parts = 0;
+    if (!range_device) {
+        parts = std::max(1, std::min(FD_VIZ_MAX_PARTS, ceil_div((long)k * px, FD_VIZ_PART_ELEMS)));
+        FD_LAUNCH(fd_viz_range, dim3((unsigned)n, (unsigned)parts), dim3(256), 0, s, map0, map1, map2, partials, px, flags & FD_VIZ_LOAD4);
+        const int rc = check_launch("fd_viz_range");
+        if (rc) return rc;
+    }
+    // 256 work-items x 4 pixels per workgroup and pass; at most 1024 workgroups per frame, the loop takes the rest
+    const long items = (long)h * panels * ((w + 3) / 4);
+    const unsigned gy = (unsigned)std::min(1024L, (items + 255) / 256);
+    FD_LAUNCH(fd_viz_paint, dim3((unsigned)n, gy), dim3(256), 0, s, x_nchw, map0, map1, map2, range_device, partials, parts, canvas, (long)pitch_bytes, h, w, k, flags);
+    return check_launch("fd_viz_paint");
+}
+
 int fd_cast_gradients(const void *src, void *dst, int64_t numel, int32_t to_bf16, void *stream)
 {
     if (!src || !dst || numel <= 0) return fail(FD_ERR_INVALID, "fd_cast_gradients: null/empty argument");

@@ -45,6 +45,9 @@ def parse_command(argv=None):
     parser.add_argument('--samples', default='', help='directory of .npz samples or one .npz file (default: seeded synthetic NYU-shaped frames)')
     parser.add_argument('--repeat', default=8, type=int, help='how many synthetic frames the default (no --samples) run evaluates')
     parser.add_argument('--dtype', default='f32', choices=['f32', 'f16', 'bf16'], help='activation storage inside the engine')
+    parser.add_argument('--comparison', default='', metavar='PATH',
+                        help='write the comparison image `rgb | target | prediction` (reference main.py:85-98) of every N-th frame to PATH (PNG)')
+    parser.add_argument('--comparison-skip', default=50, type=int, metavar='N', help='frames 0, N, 2N, ... < 8N go into the comparison image (default: 50)')
     return parser.parse_args(argv)
 
 
@@ -102,8 +105,25 @@ def _summary(avg):
     return "\n*\n" + "".join("%s=%.3f\n" % (label, getattr(avg, attr)) for label, attr in _SUMMARY) + "t_GPU=%.3f\n" % avg.gpu_time
 
 
+COMPARISON_ROWS = 8       # the reference's image holds frames 0, skip, ..., 7 * skip (main.py:85-98)
+
+
+def comparison_frames(start, count, skip, rows=COMPARISON_ROWS):
+    """The frames of a batch that go into the comparison image: [(position in the batch, row of the image)] for the global frame indices
+    start <= g < start + count with g = 0, skip, 2 skip, ... < rows * skip."""
+    if skip < 1:
+        raise ValueError("--comparison-skip must be at least 1, got %d" % skip)
+    first = (start + skip - 1) // skip
+    return [(r * skip - start, r) for r in range(first, rows) if r * skip < start + count]
+
+
 def validate(samples, model, args, device):
-    """The reference's validate() loop (main.py:63-119) over in-memory samples."""
+    """The reference's validate() loop (main.py:63-119) over in-memory samples.  With args.comparison the frames comparison_frames() names are painted
+    `rgb | target | prediction` straight from the batch's device tensors into one device canvas (fastdepth_hip.viz.paint_rows), which is written as
+    a PNG after the loop and kept as validate.img_merge (NumPy uint8).  (The reference writes its file when the loop reaches frame 8 * skip, so a
+    shorter set writes nothing; here the rows collected so far are written when the loop ends.)"""
+    comparison, skip = getattr(args, "comparison", ""), getattr(args, "comparison_skip", 50)
+    canvas, canvas_rows, seen = None, 0, 0
     average_meter = AverageMeter()
     model.eval()
     n_batches = (len(samples) + args.batch_size - 1) // args.batch_size
@@ -127,11 +147,24 @@ def validate(samples, model, args, device):
         nb = inp.size(0)
         for result in Result.evaluate_frames(pred.data, target.data):
             average_meter.update(result, gpu_time / nb, data_time / nb, 1)
+        if comparison:
+            from fastdepth_hip import viz
+            h, w = inp.shape[-2:]
+            for pos, row in comparison_frames(seen, nb, skip):
+                if canvas is None:
+                    canvas = torch.zeros((COMPARISON_ROWS * h, 3 * w, 3), dtype=torch.uint8, device=device)
+                viz.paint_rows(inp[pos:pos + 1], target[pos:pos + 1], pred[pos:pos + 1].float(), out=canvas[row * h:(row + 1) * h])
+                canvas_rows = row + 1
+            seen += nb
         end = time.time()
         if (i + 1) % args.print_freq == 0:
             print(_progress_line(i + 1, n_batches, gpu_time, result, average_meter.average()))
     avg = average_meter.average()
     print(_summary(avg))
+    if comparison and canvas is not None:
+        from fastdepth_hip import viz
+        validate.img_merge = canvas[:canvas_rows * (canvas.shape[0] // COMPARISON_ROWS)].cpu().numpy()
+        viz.save_png(validate.img_merge, comparison)
     return avg
 
 

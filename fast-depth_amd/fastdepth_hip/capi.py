@@ -197,6 +197,10 @@ def load(path=None):
     lib.fd_train_transform_scratch_bytes.restype = ctypes.c_size_t
     lib.fd_train_transform.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.fd_train_transform.restype = ctypes.c_int
+    lib.fd_depth_rows_scratch_bytes.argtypes = [i32]
+    lib.fd_depth_rows_scratch_bytes.restype = ctypes.c_size_t
+    lib.fd_depth_rows.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, ctypes.c_int64, vp, vp]
+    lib.fd_depth_rows.restype = ctypes.c_int
     lib.fd_depth_metrics_scratch_bytes.argtypes = []
     lib.fd_depth_metrics_scratch_bytes.restype = ctypes.c_size_t
     lib.fd_depth_metrics.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp]
@@ -231,6 +235,7 @@ EXPORTS = ("fd_plan_create", "fd_plan_destroy", "fd_plan_workspace_bytes", "fd_p
            "fd_train_forward", "fd_train_backward", "fd_train_backward_range", "fd_train_layer_tensor", "fd_l1_loss_scratch_bytes",
            "fd_l1_loss", "fd_l1_loss_masked", "fd_sgd_step", "fd_cast_gradients", "fd_comm_unique_id", "fd_comm_create", "fd_comm_destroy",
            "fd_train_backward_allreduce", "fd_comm_last_exchange_ms", "fd_val_transform", "fd_train_transform_scratch_bytes", "fd_train_transform",
+           "fd_depth_rows_scratch_bytes", "fd_depth_rows",
            "fd_depth_metrics_scratch_bytes", "fd_depth_metrics",
            "fd_depth_metrics_frames_scratch_bytes", "fd_depth_metrics_frames", "fd_plan_export_bytes", "fd_plan_export",
            "fd_plan_import", "fd_plan_import_weights", "fd_plan_shape", "fd_trace_begin", "fd_trace_end", "fd_last_error", "fd_version")

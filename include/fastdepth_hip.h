@@ -301,6 +301,36 @@ size_t fd_train_transform_scratch_bytes(int32_t n, int32_t out_h, int32_t out_w)
 int fd_train_transform(const void *rgb_u8, const float *depth, int32_t n, int32_t height, int32_t width, int32_t out_h, int32_t out_w,
                        const fd_aug_params *params_device, float *x_out, float *depth_out, void *scratch, void *stream);
 
+/* Comparison rows (reference utils.py:37-74 colored_depthmap / merge_into_row / merge_into_row_with_gt; deploy/data/visualize.py:22-31): per frame one
+ * canvas row block `colour frame | map0 | map1 | map2` as 8-bit RGB, the depth panels viridis-coloured over the frame's joint range -- the bytes the
+ * reference's save_image writes (its float64 image after `.astype('uint8')`), painted on the device in two launches.
+ *   x_nchw        [n][3][h][w] fp32 in [0, 1], or NULL: no colour panel
+ *   map0..map2    k = 1..3 depth maps, each [n][1][h][w] fp32; unused ones NULL, map0 required, no gap (map1 == NULL && map2 != NULL is refused)
+ *   range_device  [n][2] = (d_min, d_max) per frame in device memory, or NULL: the minimum / maximum of the frame's k maps
+ *   canvas        frame f fills rows f*h .. f*h+h-1; within a row panel j starts at byte j*w*3 (panel 0 is the colour frame when x_nchw != NULL, the maps
+ *                 follow in order); pixels are R, G, B bytes; pitch_bytes >= panels*w*3, and the bytes of a row beyond the panels are left untouched.
+ *                 A batch painted into a contiguous canvas is np.vstack of the reference's rows: k = 2 with x is merge_into_row, k = 3 with x is
+ *                 merge_into_row_with_gt, k = 1 without x is colored_depthmap (visualize.py:22-31)
+ *   scratch       fd_depth_rows_scratch_bytes(n) bytes, 4-byte aligned (may be NULL when range_device is given); nothing in it has to be zeroed or kept
+ * Any n, h, w >= 1 (no multiple-of-32 rule).  Nothing synchronises; both launches go to `stream`.  FD_ERR_INVALID, before any launch: a size <= 0,
+ * map0 == NULL, a gap in the maps, canvas == NULL, a pitch smaller than the panels, scratch == NULL while range_device == NULL.
+ * Arithmetic, pinned to the reference's:
+ *   range     d_min / d_max = the float32 minimum / maximum over all pixels of the frame's k maps, NaN-propagating like np.min / np.max (utils.py:39-41):
+ *             one NaN makes both bounds NaN and every depth pixel of THAT frame black; other frames and the colour panel are unaffected.  (Where the
+ *             reference joins several maps it uses Python's min(np.min(a), np.min(b)) (utils.py:51-52), which keeps its first argument when the other is
+ *             NaN, so there a NaN in a map other than the first is dropped from the range; here the map a NaN sits in makes no difference.)
+ *   relative  rel = (d - d_min) / (d_max - d_min) in float32 -- one subtraction, one IEEE division, no reciprocal, no contraction (utils.py:42);
+ *             t = rel * 256.0f
+ *   index     matplotlib's Colormap.__call__: t == 256 -> 255; t < 0 -> entry 0 (under); t >= 256 -> entry 255 (over); NaN -> (0, 0, 0) (bad); otherwise
+ *             int(t).  A constant frame (0 / 0) is therefore black, and +-Inf goes wherever this arithmetic sends it
+ *   colour    uint8(255 * viridis[index][c]), float64, truncated (utils.py:43): a fixed 256 x 3 table, data of the library (csrc/fd_viridis.h, generated
+ *             from matplotlib's CC0 listed-colormap data)
+ *   colour panel  uint8(double(255.0f * x)): the product in float32, truncated toward zero (utils.py:47: `255 * float32 array`, widened by hstack, cast by
+ *             save_image).  For x outside [0, 256/255) or NaN the reference's cast is platform-defined; here the value saturates to 0 / 255, NaN gives 0. */
+size_t fd_depth_rows_scratch_bytes(int32_t n);
+int fd_depth_rows(const float *x_nchw, const float *map0, const float *map1, const float *map2, int32_t n, int32_t h, int32_t w, const float *range_device,
+                  uint8_t *canvas, int64_t pitch_bytes, void *scratch, void *stream);
+
 size_t fd_depth_metrics_scratch_bytes(void);
 int fd_depth_metrics(const void *output, const void *target, int64_t numel, double *sums_device, void *scratch, void *stream);
 
