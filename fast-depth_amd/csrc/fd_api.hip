@@ -11,6 +11,7 @@
 #include "fd_kernels_gemm16_h16.h"
 #include "fd_kernels_dwpw_f32.h"
 #include "fd_kernels_dw5p.h"
+#include "fd_kernels_dwt.h"
 #include "../../include/fastdepth_hip.h"
 #include "fd_tuning.h"
 
@@ -113,6 +114,11 @@ int fd_plan_pack_weights(fd_plan *plan, const fd_layer_params *params, int32_t n
                                reinterpret_cast<float *>(plan->ws + L.w_off), bptr, L.d.cout, inner, transpose, pitch);
         int rc = check_launch("fd_pack_fold");
         if (rc) return rc;
+        if (L.dwt) {                                         // transposed layers: the bias folded in fp64 (fd_kernels_dwt.h)
+            hipLaunchKernelGGL(fd_dwt_fold_bias, dim3(ceil_div(L.d.cout, 256)), dim3(256), 0, s, q.bn_weight, q.bn_bias, q.bn_mean, q.bn_var, bn_eps, bptr, L.d.cout);
+            rc = check_launch("fd_dwt_fold_bias");
+            if (rc) return rc;
+        }
         if (L.dw5_cl) {                                      // the row-walking 5x5 kernel reads its folded taps as 16-bit pairs
             const float *wf = reinterpret_cast<const float *>(plan->ws + L.w_off);
             unsigned *wpk = reinterpret_cast<unsigned *>(plan->ws + L.wpk_off);

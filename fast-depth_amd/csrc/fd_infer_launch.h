@@ -73,6 +73,15 @@ int launch_dw(const Layer &L, const T *in, const T *skip, const float *wp, const
     return fail(FD_ERR_INVALID, "depthwise k=%d stride=%d mode=%d has no kernel", L.d.ksize, L.d.stride, L.mode);
 }
 
+// depthwise transposed conv, polyphase register-window kernel (fd_kernels_dwt.h)
+template <typename T, int ACT>
+int launch_dwt(const Layer &L, const T *in, const float *wp, const float *bias, T *out, hipStream_t s)
+{
+    if (L.d.ksize == 5) FD_LAUNCH((fd_dwt_rows<T, 5, ACT>), L.grid, dim3(256), 0, s, in, wp, bias, out, L.in_h, L.in_w, L.d.cin, L.th);
+    else FD_LAUNCH((fd_dwt_rows<T, 3, ACT>), L.grid, dim3(256), 0, s, in, wp, bias, out, L.in_h, L.in_w, L.d.cin, L.th);
+    return check_launch("fd_dwt_rows");
+}
+
 template <int ACT>
 int launch_pw(const fd_plan *plan, const Layer &L, const float *A, const float *wp, const float *bias, float *out, long M, hipStream_t s)
 {
@@ -223,6 +232,7 @@ int launch_layer(const fd_plan *p, const Layer &L, const float *x, float *y, hip
     switch (L.d.op) {
     case FD_OP_STEM: return launch_stem<T, ACT>(L, x, wpf, bias, out, p->B, s);
     case FD_OP_DW: return launch_dw<T, ACT>(L, in, skip, wpf, bias, out, s, L.dw5_cl ? reinterpret_cast<const unsigned *>(p->ws + L.wpk_off) : nullptr);
+    case FD_OP_DWT: return launch_dwt<T, ACT>(L, in, wpf, bias, out, s);
     case FD_OP_PW:
         if (L.head) {
             const int h = L.d.upsample ? L.in_h / 2 : L.in_h, w = L.d.upsample ? L.in_w / 2 : L.in_w;

@@ -112,6 +112,22 @@ int plan_layers(fd_plan *p, const fd_layer_desc *layers, size_t *woff_out)
             L.w_bytes = (size_t)d.ksize * d.ksize * d.cin * 4; L.w_elems = (size_t)d.ksize * d.ksize * d.cin;
             break;
         }
+        case FD_OP_DWT: {
+            // depthwise transposed conv, stride 2, padding (k-1)/2, output padding 1: the map doubles (fd_kernels_dwt.h)
+            if (d.src < 0 || d.cin != d.cout || (d.ksize != 3 && d.ksize != 5) || d.stride != 2 || d.upsample || d.skip >= 0 || concat || d.cin % (dtype == FD_F32 ? 4 : 8))
+                FD_BAD("layer %d: transposed depthwise needs cin==cout (multiple of %d), k in {3,5}, stride 2, no upsample / skip / concat", i, dtype == FD_F32 ? 4 : 8);
+            L.dwt = true;
+            L.out_h = 2 * L.in_h; L.out_w = 2 * L.in_w;
+            // band height (input rows): halved until the grid has >= ~4 workgroups per CU, as for fd_dw3_rows; a band re-reads one halo row (k = 5: two)
+            const int gx = ceil_div((long)L.in_w * (d.cin / 4), 256);
+            int th = L.in_h;
+            while (th > 4 && (long)gx * ceil_div(L.in_h, th) * batch < 1024) th = (th + 1) / 2;
+            L.th = th;
+            L.grid = dim3(gx, ceil_div(L.in_h, th), batch);
+            L.lds = 0;
+            L.w_bytes = (size_t)d.ksize * d.ksize * d.cin * 4; L.w_elems = (size_t)d.ksize * d.ksize * d.cin;
+            break;
+        }
         case FD_OP_PW:
             if (d.src < 0 || d.ksize != 1 || d.stride != 1 || d.cin % 4) FD_BAD("layer %d: pointwise needs k=1 stride=1 cin%%4==0", i);
             L.out_h = L.in_h; L.out_w = L.in_w;
@@ -153,8 +169,10 @@ int plan_layers(fd_plan *p, const fd_layer_desc *layers, size_t *woff_out)
         }
         if (L.lds > 160 * 1024) FD_BAD("layer %d: LDS request %zu exceeds 160 KiB", i, L.lds);
         // fd_nhwc (fd_device.h): within-image element offsets are 32-bit, formed with 24 x 24 bit multiplications
-        if ((long)L.in_h * L.in_w >= (1L << 24) || d.cin >= (1 << 24) || d.cout >= (1 << 24) || (double)L.in_h * L.in_w * std::max(d.cin, d.cout) >= 4294967296.0)
-            FD_BAD("layer %d: a %dx%d map with %d channels exceeds the kernels' 32-bit within-image addressing", i, L.in_h, L.in_w, std::max(d.cin, d.cout));
+        // (a transposed layer's larger map is its OUTPUT)
+        const int big_h = std::max(L.in_h, L.out_h), big_w = std::max(L.in_w, L.out_w);
+        if ((long)big_h * big_w >= (1L << 24) || d.cin >= (1 << 24) || d.cout >= (1 << 24) || (double)big_h * big_w * std::max(d.cin, d.cout) >= 4294967296.0)
+            FD_BAD("layer %d: a %dx%d map with %d channels exceeds the kernels' 32-bit within-image addressing", i, big_h, big_w, std::max(d.cin, d.cout));
         L.w_off = woff; woff += align_up(L.w_bytes, 256);
         if (L.dw5_cl) L.wpk_off += L.w_off;
         L.b_off = woff; woff += align_up((size_t)d.cout * 4, 256);
@@ -383,7 +401,8 @@ void plan_describe(fd_plan *p)
         const double in_esz = d.src < 0 ? 4.0 : (double)esz, out_esz = L.to_output ? 4.0 : (double)esz;   // network input / output stay fp32
         L.alg_bytes = (src_elems + skip_elems) * in_esz + out_elems * out_esz + (double)L.w_elems * (L.pw_packed_t ? esz : 4) + 2.0 * d.cout * 4;
         p->alg_bytes += L.alg_bytes;
-        const double taps = d.op == FD_OP_STEM ? 27.0 : (d.op == FD_OP_DW ? (double)d.ksize * d.ksize : (double)d.cin);
+        // (transposed depthwise, polyphase: k^2 / 4 multiply-adds per output)
+        const double taps = d.op == FD_OP_STEM ? 27.0 : (d.op == FD_OP_DW ? (double)d.ksize * d.ksize : (d.op == FD_OP_DWT ? d.ksize * d.ksize / 4.0 : (double)d.cin));
         const double mac_px = L.head && d.upsample ? (double)L.out_h * L.out_w : (double)L.out_h * L.out_w;
         L.alg_flops = 2.0 * batch * mac_px * d.cout * taps;
         p->alg_flops += L.alg_flops;
@@ -400,6 +419,9 @@ void plan_describe(fd_plan *p)
                      L.fuse_head >= 0 ? " + the 32->1 head on the accumulators" : "");
         else if (d.op == FD_OP_STEM)
             snprintf(buf, sizeof buf, "stem3x3s2<mfma 32x32x2, LDS-staged rows, 256 px per workgroup> grid=%ux%u lds=%zu", L.grid.x, L.grid.y, L.lds);
+        else if (d.op == FD_OP_DWT)
+            snprintf(buf, sizeof buf, "dwt_rows<k%d s2, polyphase: %d taps per 2x2 output quad, 4 channels per work-item> %d input rows per band, grid=%ux%ux%u, no LDS",
+                     d.ksize, d.ksize == 5 ? 25 : 9, L.th, L.grid.x, L.grid.y, L.grid.z);
         else if (d.op == FD_OP_DW && L.dw5_cl)
             snprintf(buf, sizeof buf, "dw5_rows<k5 s1 mode2, pixel pairs + dot2, %d channel lanes per strip> bands of %d rows, %d strip groups, %d channels per block, grid=%ux%ux%u, no LDS",
                      L.dw5_cl, L.dw5_bh, L.dw5_groups, L.dw5_cbs, L.grid.x, L.grid.y, L.grid.z);
@@ -424,6 +446,7 @@ void plan_describe(fd_plan *p)
         if (L.skipped || L.fused_into >= 0) buf[0] = 0;
         else if (L.dwpw) snprintf(buf, sizeof buf, "fd_dwpw_f32<%d, %d, %d, %d, %d, %d, %d, %d, 0>", p->layers[L.fused_dw].d.ksize, p->layers[L.fused_dw].d.stride, p->layers[L.fused_dw].mode, d.act, L.dp_wm, L.dp_nt, L.dp_nld, L.fuse_head >= 0 ? 1 : 0);
         else if (d.op == FD_OP_STEM) snprintf(buf, sizeof buf, "fd_stem3x3s2<%s, %d, %d>", tn, d.act, L.chunk);
+        else if (d.op == FD_OP_DWT) snprintf(buf, sizeof buf, "fd_dwt_rows<%s, %d, %d>", tn, d.ksize, d.act);
         else if (d.op == FD_OP_DW && L.dw5_cl) snprintf(buf, sizeof buf, "fd_dw5_rows<%s, %d, %d>", tn, d.act, L.dw5_cl);
         else if (d.op == FD_OP_DW && L.dw_rows) snprintf(buf, sizeof buf, "fd_dw3_rows%s<%s, %d, %d>", L.dw_rows8 ? "8" : "", tn, d.stride, d.act);
         else if (d.op == FD_OP_DW) snprintf(buf, sizeof buf, "fd_dwconv<%s, %d, %d, %d, %d, %d>", tn, d.ksize, d.stride, L.mode, d.act, L.dw_n);

@@ -73,6 +73,7 @@ struct Layer {
     int dp_th = 0, dp_tw = 0 /* log2 of the tile width */, dp_tiles_x = 0, dp_wm = 0, dp_nt = 0, dp_nld = 0, dp_xcd = 0;
     bool dw_rows = false;        // register-window 3x3 kernel (fd_dw3_rows_f32) instead of the LDS-tiled one
     bool dw_rows8 = false;       // ... its 16-bit variant with eight channels per work-item (fd_dw3_rows8)
+    bool dwt = false;            // transposed depthwise layer (FD_OP_DWT): the polyphase register-window kernel fd_dwt_rows, th input rows per band
     // stem
     int chunk = 0;
     // pw

@@ -5,7 +5,8 @@ reference checkpoints are whole pickled modules whose __init__ is bypassed on lo
 and pruned models carry irregular widths.  The walk restates the reference's forward order
 (models.py:706-732): conv0..conv13, skip taps after conv1/conv3/conv5, decode_conv1..5 each followed
 by nearest x2 and (after 2/3/4) the additive skip, then decode_conv6.  Upsample + add are not layers of
-their own: they become `upsample` / `skip` attributes of the layer that consumes the result.
+their own: they become `upsample` / `skip` attributes of the layer that consumes the result.  The DeConv decoder of the no-skip sibling
+(`decoder.convt1..5`, `decoder.convf`) upsamples nowhere: its depthwise transposed convolutions are layers of their own kind (FD_OP_DWT).
 """
 import torch.nn as nn
 
@@ -38,6 +39,15 @@ def _units(seq):
     out = []
     for i in range(0, len(flat), 3):
         conv, bn, act = flat[i:i + 3]
+        if isinstance(conv, nn.ConvTranspose2d) and isinstance(bn, nn.BatchNorm2d):
+            # the one transposed convolution with a kernel (FD_OP_DWT): depthwise, k in {3, 5}, doubling the map (reference models.py:89-99)
+            k = conv.kernel_size[0]
+            if (conv.bias is not None or conv.kernel_size != (k, k) or k not in (3, 5) or conv.stride != (2, 2) or conv.padding != ((k - 1) // 2,) * 2
+                    or conv.output_padding != (1, 1) or conv.dilation != (1, 1) or not conv.groups == conv.in_channels == conv.out_channels):
+                raise capi.FastDepthError("transposed conv %r is outside the FastDepth path (only depthwise k in {3, 5}, stride 2, padding (k-1)/2, "
+                                          "output_padding 1, no bias, no dilation has a kernel)" % (conv,))
+            out.append((conv, bn, _act_of(act)))
+            continue
         if not (isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d)):
             raise capi.FastDepthError("expected Conv2d, BatchNorm2d, activation; got %r, %r" % (conv, bn))
         if conv.bias is not None or conv.dilation != (1, 1) or conv.padding != (conv.kernel_size[0] // 2,) * 2:
@@ -51,7 +61,9 @@ class Layer:
 
     def __init__(self, name, conv, bn, act, src, upsample=0, skip=-1, concat=0):
         k = conv.kernel_size[0]
-        if conv.groups == 1 and k == 3:
+        if isinstance(conv, nn.ConvTranspose2d):       # (validated by _units)
+            op = capi.FD_OP_DWT
+        elif conv.groups == 1 and k == 3:
             op = capi.FD_OP_STEM
         elif conv.groups == conv.in_channels == conv.out_channels and k in (3, 5):
             op = capi.FD_OP_DW
@@ -72,6 +84,14 @@ def _layers_of_plain(model):
         for j, (conv, bn, act) in enumerate(_units(model.mobilenet[i])):
             layers.append(Layer("mobilenet.%d.%d" % (i, 3 * j), conv, bn, act, src))
             src = len(layers) - 1
+    if hasattr(model.decoder, "convt1"):
+        # DeConv decoder (reference models.py:145-180): convt1..5 = (transposed depthwise, pointwise), then convf; the transposed layers
+        # double the map themselves, so nothing is upsampled
+        for name in ["convt%d" % j for j in range(1, 6)] + ["convf"]:
+            for q, (conv, bn, act) in enumerate(_units(getattr(model.decoder, name))):
+                layers.append(Layer("decoder.%s.%d" % (name, q), conv, bn, act, src))
+                src = len(layers) - 1
+        return layers
     pending_up = 0
     for j in range(1, 7):
         for q, (conv, bn, act) in enumerate(_units(getattr(model.decoder, "conv%d" % j))):

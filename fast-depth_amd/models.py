@@ -25,7 +25,7 @@ import torch.nn as nn
 
 import imagenet.mobilenet as _mobilenet
 
-__all__ = ["MobileNetSkipAdd", "MobileNetSkipConcat", "MobileNet", "NNConv", "choose_decoder", "depthwise", "pointwise", "weights_init", "PRUNED_CHANNELS"]
+__all__ = ["MobileNetSkipAdd", "MobileNetSkipConcat", "MobileNet", "NNConv", "DeConv", "choose_decoder", "depthwise", "pointwise", "weights_init", "PRUNED_CHANNELS"]
 
 # Channel plan of `mobilenet-nnconv5dw-skipadd-pruned`, reconstructed from the reference's TVM tuning
 # log (tvm_compile/tuning/tx2-gpu.mobilenet-nnconv5dw-skipadd-pruned.trials=2000.stop=600.log:1-38,
@@ -65,6 +65,16 @@ def depthwise(in_channels, kernel_size):
 def pointwise(in_channels, out_channels):
     """1x1 conv (no bias) + BN + ReLU; reference models.py:70-75."""
     return nn.Sequential(nn.Conv2d(in_channels, out_channels, 1, 1, 0, bias=False), *_bn_relu(out_channels))
+
+
+def depthwise_transposed(channels, kernel_size):
+    """k x k depthwise transposed conv that doubles the map (stride 2, pad (k-1)/2, output_padding 1, no bias) + BN + ReLU;
+    reference models.py:89-99 (convt_dw)."""
+    if kernel_size % 2 != 1:
+        raise AssertionError("deconv parameters incorrect. kernel={}".format(kernel_size))
+    return nn.Sequential(
+        nn.ConvTranspose2d(channels, channels, kernel_size, stride=2, padding=kernel_size // 2, output_padding=1,
+                           bias=False, groups=channels), *_bn_relu(channels))
 
 
 class _HipForward(nn.Module):
@@ -122,12 +132,33 @@ class NNConv(nn.Module):
         self.conv6 = pointwise(width, 1)
 
 
+class DeConv(nn.Module):
+    """Transposed-convolution decoder, depthwise-separable form (reference models.py:145-180 with dw=True):
+    convt1..convt5 = Sequential(depthwise_transposed(C, k), pointwise(C, C/2)) for C = 1024..64, convf = pointwise(32, 1).  Every
+    transposed layer doubles the map, so the reference's forward is the plain chain.  Parameter container only (the HIP engine
+    executes it as part of `MobileNet`; the transposed layers run on the polyphase kernel fd_dwt_rows).  The dense variant
+    (dw=False: full k x k transposed convolutions) is outside this package's kernels."""
+
+    def __init__(self, kernel_size, dw):
+        super().__init__()
+        if not dw:
+            raise NotImplementedError("fast-depth_amd implements the depthwise-separable decoders ('deconv5dw', 'deconv3dw'); "
+                                      "the dense DeConv decoder is not on the accelerated path")
+        width = 1024
+        for j in range(1, 6):
+            setattr(self, 'convt{}'.format(j), nn.Sequential(depthwise_transposed(width, kernel_size), pointwise(width, width // 2)))
+            width //= 2
+        self.convf = pointwise(width, 1)
+
+
 def choose_decoder(decoder):
     """Reference models.py:335-360, restricted to the decoders whose layers are on the accelerated path."""
     if decoder in ('nnconv5dw', 'nnconv3dw'):
         model = NNConv(int(decoder[6]), True)
+    elif decoder in ('deconv5dw', 'deconv3dw'):
+        model = DeConv(int(decoder[6]), True)
     else:
-        raise NotImplementedError("decoder {!r}: only 'nnconv5dw' / 'nnconv3dw' are built by fast-depth_amd "
+        raise NotImplementedError("decoder {!r}: only 'nnconv5dw' / 'nnconv3dw' / 'deconv5dw' / 'deconv3dw' are built by fast-depth_amd "
                                   "(SURVEY.md 8(f) row f-3)".format(decoder))
     model.apply(weights_init)
     return model
@@ -137,7 +168,7 @@ class MobileNet(_HipForward):
     """MobileNet-v1 encoder + decoder WITHOUT skip connections -- `MobileNet(decoder, output_size, in_channels=3,
     pretrained=True)` as in reference models.py:420-460 (runs on the same kernels as
     MobileNetSkipAdd, with `skip = -1` everywhere).  Attribute tree and state_dict keys follow the reference:
-    `mobilenet.0 .. mobilenet.13`, `decoder.conv1 .. decoder.conv6`."""
+    `mobilenet.0 .. mobilenet.13`, `decoder.conv1 .. decoder.conv6` (NNConv) or `decoder.convt1 .. decoder.convt5`, `decoder.convf` (DeConv)."""
 
     def __init__(self, decoder, output_size, in_channels=3, pretrained=True):
         super().__init__()

@@ -43,11 +43,15 @@ extern "C" {
 /* storage / arithmetic type of activations and packed weights (accumulation is always fp32) */
 enum fd_dtype { FD_F32 = 0, FD_F16 = 1, FD_BF16 = 2 };
 
-/* fused layer kinds: every one is Conv2d(bias=False) + BatchNorm2d + activation */
+/* fused layer kinds: every one is Conv2d / ConvTranspose2d(bias=False) + BatchNorm2d + activation */
 enum fd_op {
     FD_OP_STEM = 0, /* dense 3x3 conv, stride 2, NCHW-planar in -> NHWC out   (mobilenet.py:22-27,41)  */
     FD_OP_DW = 1,   /* depthwise k x k conv (k = 3 or 5), stride 1 or 2        (mobilenet.py:31-33; models.py:61-68) */
-    FD_OP_PW = 2    /* pointwise 1x1 conv = GEMM over channels                 (mobilenet.py:35-37; models.py:70-75) */
+    FD_OP_PW = 2,   /* pointwise 1x1 conv = GEMM over channels                 (mobilenet.py:35-37; models.py:70-75) */
+    FD_OP_DWT = 3   /* depthwise TRANSPOSED k x k conv (k = 3 or 5): ConvTranspose2d(C, C, k, stride 2, padding (k-1)/2, output_padding 1, groups=C), the
+                     * map-doubling unit of the DeConv decoder (models.py:89-99, 145-180).  cin == cout (fp32: a multiple of 4, 16-bit plans: of 8), stride = 2,
+                     * upsample = 0, skip = -1, concat = 0; the output map is 2 x the input map in both directions.  conv_weight is torch's [cin][1][k][k].
+                     * Inference plans only: fd_train_plan_create refuses a plan that contains one (FD_ERR_INVALID, the message names the layer). */
 };
 enum fd_act { FD_ACT_NONE = 0, FD_ACT_RELU = 1, FD_ACT_RELU6 = 2 };
 
@@ -66,9 +70,9 @@ enum fd_act { FD_ACT_NONE = 0, FD_ACT_RELU = 1, FD_ACT_RELU6 = 2 };
 typedef struct fd_layer_desc {
     int32_t op;       /* enum fd_op */
     int32_t cin;
-    int32_t cout;     /* == cin for FD_OP_DW */
+    int32_t cout;     /* == cin for FD_OP_DW / FD_OP_DWT */
     int32_t ksize;    /* 3 (stem, encoder dw), 5 (decoder dw), 1 (pw) */
-    int32_t stride;   /* 1 or 2 */
+    int32_t stride;   /* 1 or 2 (FD_OP_DWT: 2, the factor by which the map GROWS) */
     int32_t act;      /* enum fd_act */
     int32_t src;      /* index of the layer whose output feeds this one; -1 = network input */
     int32_t upsample; /* 1: the input is the nearest-neighbour x2 upsampling of src's output (models.py:723) */
