@@ -82,6 +82,15 @@ int launch_dwt(const Layer &L, const T *in, const float *wp, const float *bias, 
     return check_launch("fd_dwt_rows");
 }
 
+// depthwise conv on the 2x pixel shuffle of the producer's output, register-window kernel (fd_kernels_dws.h); in_h x in_w is the shuffled map
+template <typename T, int ACT>
+int launch_dws(const Layer &L, const T *in, const float *wp, const float *bias, T *out, hipStream_t s)
+{
+    if (L.d.ksize == 5) FD_LAUNCH((fd_dws_rows<T, 5, ACT>), L.grid, dim3(256), 0, s, in, wp, bias, out, L.in_h / 2, L.in_w / 2, L.d.cin, L.th);
+    else FD_LAUNCH((fd_dws_rows<T, 3, ACT>), L.grid, dim3(256), 0, s, in, wp, bias, out, L.in_h / 2, L.in_w / 2, L.d.cin, L.th);
+    return check_launch("fd_dws_rows");
+}
+
 template <int ACT>
 int launch_pw(const fd_plan *plan, const Layer &L, const float *A, const float *wp, const float *bias, float *out, long M, hipStream_t s)
 {
@@ -233,6 +242,10 @@ int launch_layer(const fd_plan *p, const Layer &L, const float *x, float *y, hip
     case FD_OP_STEM: return launch_stem<T, ACT>(L, x, wpf, bias, out, p->B, s);
     case FD_OP_DW: return launch_dw<T, ACT>(L, in, skip, wpf, bias, out, s, L.dw5_cl ? reinterpret_cast<const unsigned *>(p->ws + L.wpk_off) : nullptr);
     case FD_OP_DWT: return launch_dwt<T, ACT>(L, in, wpf, bias, out, s);
+    case FD_OP_DWS: return launch_dws<T, ACT>(L, in, wpf, bias, out, s);
+    case FD_OP_PWS:
+        FD_LAUNCH((fd_head_shuffle<T, ACT>), L.grid, dim3(256), 0, s, in, wpf, bias, y, (long)p->B * L.out_h * L.out_w, L.out_h, L.out_w, L.d.cin);
+        return check_launch("fd_head_shuffle");
     case FD_OP_PW:
         if (L.head) {
             const int h = L.d.upsample ? L.in_h / 2 : L.in_h, w = L.d.upsample ? L.in_w / 2 : L.in_w;

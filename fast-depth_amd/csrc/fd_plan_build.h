@@ -27,9 +27,11 @@ int plan_layers(fd_plan *p, const fd_layer_desc *layers, size_t *woff_out)
         if (concat) {
             L.csplit = src_c;
             if (src_c + p->layers[d.skip].d.cout != d.cin || src_c % 4) FD_BAD("layer %d: concat of %d + %d channels does not give cin %d", i, src_c, p->layers[d.skip].d.cout, d.cin);
+        } else if (d.op == FD_OP_DWS) {                        // reads through the 2x pixel shuffle: a quarter of the channels, twice the map
+            if (d.src < 0 || src_c != 4 * d.cin) FD_BAD("layer %d: pixel-shuffle depthwise needs 4 * cin (%d) == producer channels %d", i, d.cin, src_c);
         } else if (src_c != d.cin) FD_BAD("layer %d: cin %d != producer channels %d", i, d.cin, src_c);
-        L.in_h = d.upsample ? 2 * src_h : src_h;
-        L.in_w = d.upsample ? 2 * src_w : src_w;
+        L.in_h = (d.upsample || d.op == FD_OP_DWS) ? 2 * src_h : src_h;
+        L.in_w = (d.upsample || d.op == FD_OP_DWS) ? 2 * src_w : src_w;
         if (d.skip >= 0) {
             const Layer &S = p->layers[d.skip];
             if (!d.upsample) FD_BAD("layer %d: skip without upsample is not part of this path", i);
@@ -128,6 +130,33 @@ int plan_layers(fd_plan *p, const fd_layer_desc *layers, size_t *woff_out)
             L.w_bytes = (size_t)d.ksize * d.ksize * d.cin * 4; L.w_elems = (size_t)d.ksize * d.ksize * d.cin;
             break;
         }
+        case FD_OP_DWS: {
+            // depthwise conv, stride 1, on the 2x pixel shuffle of the producer's output (fd_kernels_dws.h): in_h x in_w is the shuffled map
+            if (d.cin != d.cout || (d.ksize != 3 && d.ksize != 5) || d.stride != 1 || d.upsample || d.skip >= 0 || concat || d.cin % (dtype == FD_F32 ? 1 : 2))
+                FD_BAD("layer %d: pixel-shuffle depthwise needs cin==cout (16-bit plans: a multiple of 2), k in {3,5}, stride 1, no upsample / skip / concat", i);
+            L.dws = true;
+            L.out_h = L.in_h; L.out_w = L.in_w;
+            // band height (SOURCE rows): halved until the grid has >= ~4 workgroups per CU, as for fd_dwt_rows; a band re-reads two halo rows
+            const int sh = L.in_h / 2, sw = L.in_w / 2;
+            const int gx = ceil_div((long)sw * (d.cin / (dtype == FD_F32 ? 1 : 2)), 256);
+            int th = sh;
+            while (th > 4 && (long)gx * ceil_div(sh, th) * batch < 1024) th = (th + 1) / 2;
+            L.th = th;
+            L.grid = dim3(gx, ceil_div(sh, th), batch);
+            L.lds = 0;
+            L.w_bytes = (size_t)d.ksize * d.ksize * d.cin * 4; L.w_elems = (size_t)d.ksize * d.ksize * d.cin;
+            break;
+        }
+        case FD_OP_PWS:
+            // pointwise cin -> 4 whose outputs are the 2 x 2 quads of the fp32 network output (fd_kernels_dws.h); fp32 weights [cin][4] in every plan
+            if (d.src < 0 || d.ksize != 1 || d.stride != 1 || d.cin % 4 || d.cin > 64 || d.cout != 4 || d.upsample || d.skip >= 0 || concat)
+                FD_BAD("layer %d: pixel-shuffle head needs k=1 stride=1, cin%%4==0, cin<=64, cout==4, no upsample / skip / concat", i);
+            if (i != n_layers - 1) FD_BAD("layer %d: the pixel-shuffle head (FD_OP_PWS) is only valid as the last layer", i);
+            L.pws = true;
+            L.out_h = L.in_h; L.out_w = L.in_w;
+            L.w_bytes = (size_t)d.cin * 4 * 4; L.w_elems = (size_t)d.cin * 4;
+            L.grid = dim3(ceil_div((long)batch * L.out_h * L.out_w, 256));
+            break;
         case FD_OP_PW:
             if (d.src < 0 || d.ksize != 1 || d.stride != 1 || d.cin % 4) FD_BAD("layer %d: pointwise needs k=1 stride=1 cin%%4==0", i);
             L.out_h = L.in_h; L.out_w = L.in_w;
@@ -180,7 +209,7 @@ int plan_layers(fd_plan *p, const fd_layer_desc *layers, size_t *woff_out)
         L.pw_packed_t = (d.op == FD_OP_PW && !L.head && dtype != FD_F32);
     }
     Layer &last = p->layers.back();
-    if (last.d.cout != 1 || last.out_h != height || last.out_w != width)
+    if (last.pws ? (2 * last.out_h != height || 2 * last.out_w != width) : (last.d.cout != 1 || last.out_h != height || last.out_w != width))
         FD_BAD("the last layer must produce the [B,1,%d,%d] network output (got %dx%dx%d)", height, width, last.out_h, last.out_w, last.d.cout);
 #undef FD_BAD
     last.to_output = true;
@@ -395,6 +424,7 @@ void plan_describe(fd_plan *p)
         Layer &L = p->layers[i];
         const fd_layer_desc &d = L.d;
         const int c_src = L.csplit ? L.csplit : d.cin, c_skip = L.csplit ? d.cin - L.csplit : d.cin;
+        // (a pixel-shuffle depthwise layer reads in_h/2 x in_w/2 pixels of 4 cin channels: the same element count as its shuffled input map)
         const double src_elems = (double)batch * (d.upsample ? (L.in_h / 2) * (L.in_w / 2) : L.in_h * L.in_w) * c_src;
         const double skip_elems = d.skip >= 0 ? (double)batch * L.in_h * L.in_w * c_skip : 0.0;
         const double out_elems = (double)batch * L.out_h * L.out_w * d.cout;
@@ -402,7 +432,7 @@ void plan_describe(fd_plan *p)
         L.alg_bytes = (src_elems + skip_elems) * in_esz + out_elems * out_esz + (double)L.w_elems * (L.pw_packed_t ? esz : 4) + 2.0 * d.cout * 4;
         p->alg_bytes += L.alg_bytes;
         // (transposed depthwise, polyphase: k^2 / 4 multiply-adds per output)
-        const double taps = d.op == FD_OP_STEM ? 27.0 : (d.op == FD_OP_DW ? (double)d.ksize * d.ksize : (d.op == FD_OP_DWT ? d.ksize * d.ksize / 4.0 : (double)d.cin));
+        const double taps = d.op == FD_OP_STEM ? 27.0 : ((d.op == FD_OP_DW || d.op == FD_OP_DWS) ? (double)d.ksize * d.ksize : (d.op == FD_OP_DWT ? d.ksize * d.ksize / 4.0 : (double)d.cin));
         const double mac_px = L.head && d.upsample ? (double)L.out_h * L.out_w : (double)L.out_h * L.out_w;
         L.alg_flops = 2.0 * batch * mac_px * d.cout * taps;
         p->alg_flops += L.alg_flops;
@@ -422,6 +452,11 @@ void plan_describe(fd_plan *p)
         else if (d.op == FD_OP_DWT)
             snprintf(buf, sizeof buf, "dwt_rows<k%d s2, polyphase: %d taps per 2x2 output quad, 4 channels per work-item> %d input rows per band, grid=%ux%ux%u, no LDS",
                      d.ksize, d.ksize == 5 ? 25 : 9, L.th, L.grid.x, L.grid.y, L.grid.z);
+        else if (d.op == FD_OP_DWS)
+            snprintf(buf, sizeof buf, "dws_rows<k%d s1 on the 2x pixel shuffle of the producer, %d output channels (16 source bytes) per work-item> %d source rows per band, grid=%ux%ux%u, no LDS",
+                     d.ksize, dtype == FD_F32 ? 1 : 2, L.th, L.grid.x, L.grid.y, L.grid.z);
+        else if (d.op == FD_OP_PWS)
+            snprintf(buf, sizeof buf, "head_shuffle<%d -> 4, written as the 2x2 quads of the network output> grid=%u", d.cin, L.grid.x);
         else if (d.op == FD_OP_DW && L.dw5_cl)
             snprintf(buf, sizeof buf, "dw5_rows<k5 s1 mode2, pixel pairs + dot2, %d channel lanes per strip> bands of %d rows, %d strip groups, %d channels per block, grid=%ux%ux%u, no LDS",
                      L.dw5_cl, L.dw5_bh, L.dw5_groups, L.dw5_cbs, L.grid.x, L.grid.y, L.grid.z);
@@ -447,6 +482,8 @@ void plan_describe(fd_plan *p)
         else if (L.dwpw) snprintf(buf, sizeof buf, "fd_dwpw_f32<%d, %d, %d, %d, %d, %d, %d, %d, 0>", p->layers[L.fused_dw].d.ksize, p->layers[L.fused_dw].d.stride, p->layers[L.fused_dw].mode, d.act, L.dp_wm, L.dp_nt, L.dp_nld, L.fuse_head >= 0 ? 1 : 0);
         else if (d.op == FD_OP_STEM) snprintf(buf, sizeof buf, "fd_stem3x3s2<%s, %d, %d>", tn, d.act, L.chunk);
         else if (d.op == FD_OP_DWT) snprintf(buf, sizeof buf, "fd_dwt_rows<%s, %d, %d>", tn, d.ksize, d.act);
+        else if (d.op == FD_OP_DWS) snprintf(buf, sizeof buf, "fd_dws_rows<%s, %d, %d>", tn, d.ksize, d.act);
+        else if (d.op == FD_OP_PWS) snprintf(buf, sizeof buf, "fd_head_shuffle<%s, %d>", tn, d.act);
         else if (d.op == FD_OP_DW && L.dw5_cl) snprintf(buf, sizeof buf, "fd_dw5_rows<%s, %d, %d>", tn, d.act, L.dw5_cl);
         else if (d.op == FD_OP_DW && L.dw_rows) snprintf(buf, sizeof buf, "fd_dw3_rows%s<%s, %d, %d>", L.dw_rows8 ? "8" : "", tn, d.stride, d.act);
         else if (d.op == FD_OP_DW) snprintf(buf, sizeof buf, "fd_dwconv<%s, %d, %d, %d, %d, %d>", tn, d.ksize, d.stride, L.mode, d.act, L.dw_n);

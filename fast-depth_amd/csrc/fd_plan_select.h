@@ -74,6 +74,8 @@ struct Layer {
     bool dw_rows = false;        // register-window 3x3 kernel (fd_dw3_rows_f32) instead of the LDS-tiled one
     bool dw_rows8 = false;       // ... its 16-bit variant with eight channels per work-item (fd_dw3_rows8)
     bool dwt = false;            // transposed depthwise layer (FD_OP_DWT): the polyphase register-window kernel fd_dwt_rows, th input rows per band
+    bool dws = false;            // depthwise layer on the pixel shuffle of its producer (FD_OP_DWS): fd_dws_rows, th source rows per band
+    bool pws = false;            // pointwise cin -> 4 written through the pixel shuffle as the network output (FD_OP_PWS): fd_head_shuffle
     // stem
     int chunk = 0;
     // pw

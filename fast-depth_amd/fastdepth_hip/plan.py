@@ -7,6 +7,8 @@ and pruned models carry irregular widths.  The walk restates the reference's for
 by nearest x2 and (after 2/3/4) the additive skip, then decode_conv6.  Upsample + add are not layers of
 their own: they become `upsample` / `skip` attributes of the layer that consumes the result.  The DeConv decoder of the no-skip sibling
 (`decoder.convt1..5`, `decoder.convf`) upsamples nowhere: its depthwise transposed convolutions are layers of their own kind (FD_OP_DWT).
+The ShuffleConv decoder (`decoder.conv1..4`) puts a 2x pixel shuffle before each unit and after the last: its depthwise layers read through the
+shuffle (FD_OP_DWS) and its last pointwise layer writes the network output through it (FD_OP_PWS).
 """
 import torch.nn as nn
 
@@ -59,9 +61,14 @@ def _units(seq):
 class Layer:
     __slots__ = ("conv", "bn", "desc", "name")
 
-    def __init__(self, name, conv, bn, act, src, upsample=0, skip=-1, concat=0):
+    def __init__(self, name, conv, bn, act, src, upsample=0, skip=-1, concat=0, op=None):
+        # op: told by the walk where the module alone does not say it (the pixel-shuffle layers are plain depthwise / pointwise convolutions)
         k = conv.kernel_size[0]
-        if isinstance(conv, nn.ConvTranspose2d):       # (validated by _units)
+        if op is not None:
+            want = (conv.groups == conv.in_channels == conv.out_channels and k in (3, 5)) if op == capi.FD_OP_DWS else (conv.groups == 1 and k == 1)
+            if op not in (capi.FD_OP_DWS, capi.FD_OP_PWS) or not want or conv.stride != (1, 1):
+                raise capi.FastDepthError("%s: conv %r cannot run as op %r" % (name, conv, op))
+        elif isinstance(conv, nn.ConvTranspose2d):     # (validated by _units)
             op = capi.FD_OP_DWT
         elif conv.groups == 1 and k == 3:
             op = capi.FD_OP_STEM
@@ -90,6 +97,18 @@ def _layers_of_plain(model):
         for name in ["convt%d" % j for j in range(1, 6)] + ["convf"]:
             for q, (conv, bn, act) in enumerate(_units(getattr(model.decoder, name))):
                 layers.append(Layer("decoder.%s.%d" % (name, q), conv, bn, act, src))
+                src = len(layers) - 1
+        return layers
+    if hasattr(model.decoder, "conv4") and not hasattr(model.decoder, "conv5") and not hasattr(model.decoder, "conv6"):
+        # ShuffleConv decoder (reference models.py:296-333): pixel_shuffle(2) before each of conv1..4 = (depthwise, pointwise) and after conv4.
+        # The depthwise layers read through the shuffle, the last pointwise layer writes the network output through it: nothing is upsampled
+        for j in range(1, 5):
+            units = _units(getattr(model.decoder, "conv%d" % j))
+            if len(units) != 2:
+                raise capi.FastDepthError("decoder.conv%d: expected a (depthwise, pointwise) pair, got %d units" % (j, len(units)))
+            for q, (conv, bn, act) in enumerate(units):
+                op = capi.FD_OP_DWS if q == 0 else (capi.FD_OP_PWS if j == 4 else None)
+                layers.append(Layer("decoder.conv%d.%d" % (j, q), conv, bn, act, src, op=op))
                 src = len(layers) - 1
         return layers
     pending_up = 0

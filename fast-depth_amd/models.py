@@ -25,7 +25,7 @@ import torch.nn as nn
 
 import imagenet.mobilenet as _mobilenet
 
-__all__ = ["MobileNetSkipAdd", "MobileNetSkipConcat", "MobileNet", "NNConv", "DeConv", "choose_decoder", "depthwise", "pointwise", "weights_init", "PRUNED_CHANNELS"]
+__all__ = ["MobileNetSkipAdd", "MobileNetSkipConcat", "MobileNet", "NNConv", "DeConv", "ShuffleConv", "choose_decoder", "depthwise", "pointwise", "weights_init", "PRUNED_CHANNELS"]
 
 # Channel plan of `mobilenet-nnconv5dw-skipadd-pruned`, reconstructed from the reference's TVM tuning
 # log (tvm_compile/tuning/tx2-gpu.mobilenet-nnconv5dw-skipadd-pruned.trials=2000.stop=600.log:1-38,
@@ -151,14 +151,32 @@ class DeConv(nn.Module):
         self.convf = pointwise(width, 1)
 
 
+class ShuffleConv(nn.Module):
+    """Pixel-shuffle decoder, depthwise-separable form (reference models.py:296-333 with dw=True): conv1..conv4 =
+    Sequential(depthwise(C, k), pointwise(C, C)) for C = 256, 64, 16, 4; the reference's forward puts F.pixel_shuffle(x, 2) before each of
+    them and after conv4, which turns the last 4-channel map into the [B, 1, H, W] output.  Parameter container only (the HIP engine
+    executes it as part of `MobileNet`: the depthwise layers read through the shuffle on fd_dws_rows, conv4's pointwise layer writes the
+    output through it on fd_head_shuffle).  The dense variant (dw=False: full k x k convolutions) is outside this package's kernels."""
+
+    def __init__(self, kernel_size, dw):
+        super().__init__()
+        if not dw:
+            raise NotImplementedError("fast-depth_amd implements the depthwise-separable decoders ('shuffle5dw', 'shuffle3dw'); "
+                                      "the dense ShuffleConv decoder is not on the accelerated path")
+        for j, width in enumerate((256, 64, 16, 4), 1):
+            setattr(self, 'conv{}'.format(j), nn.Sequential(depthwise(width, kernel_size), pointwise(width, width)))
+
+
 def choose_decoder(decoder):
     """Reference models.py:335-360, restricted to the decoders whose layers are on the accelerated path."""
     if decoder in ('nnconv5dw', 'nnconv3dw'):
         model = NNConv(int(decoder[6]), True)
     elif decoder in ('deconv5dw', 'deconv3dw'):
         model = DeConv(int(decoder[6]), True)
+    elif decoder in ('shuffle5dw', 'shuffle3dw'):
+        model = ShuffleConv(int(decoder[7]), True)
     else:
-        raise NotImplementedError("decoder {!r}: only 'nnconv5dw' / 'nnconv3dw' / 'deconv5dw' / 'deconv3dw' are built by fast-depth_amd "
+        raise NotImplementedError("decoder {!r}: only 'nnconv5dw' / 'nnconv3dw' / 'deconv5dw' / 'deconv3dw' / 'shuffle5dw' / 'shuffle3dw' are built by fast-depth_amd "
                                   "(SURVEY.md 8(f) row f-3)".format(decoder))
     model.apply(weights_init)
     return model
@@ -168,7 +186,8 @@ class MobileNet(_HipForward):
     """MobileNet-v1 encoder + decoder WITHOUT skip connections -- `MobileNet(decoder, output_size, in_channels=3,
     pretrained=True)` as in reference models.py:420-460 (runs on the same kernels as
     MobileNetSkipAdd, with `skip = -1` everywhere).  Attribute tree and state_dict keys follow the reference:
-    `mobilenet.0 .. mobilenet.13`, `decoder.conv1 .. decoder.conv6` (NNConv) or `decoder.convt1 .. decoder.convt5`, `decoder.convf` (DeConv)."""
+    `mobilenet.0 .. mobilenet.13`, `decoder.conv1 .. decoder.conv6` (NNConv) or `decoder.convt1 .. decoder.convt5`, `decoder.convf` (DeConv)
+    or `decoder.conv1 .. decoder.conv4` (ShuffleConv)."""
 
     def __init__(self, decoder, output_size, in_channels=3, pretrained=True):
         super().__init__()

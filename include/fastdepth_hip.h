@@ -48,10 +48,19 @@ enum fd_op {
     FD_OP_STEM = 0, /* dense 3x3 conv, stride 2, NCHW-planar in -> NHWC out   (mobilenet.py:22-27,41)  */
     FD_OP_DW = 1,   /* depthwise k x k conv (k = 3 or 5), stride 1 or 2        (mobilenet.py:31-33; models.py:61-68) */
     FD_OP_PW = 2,   /* pointwise 1x1 conv = GEMM over channels                 (mobilenet.py:35-37; models.py:70-75) */
-    FD_OP_DWT = 3   /* depthwise TRANSPOSED k x k conv (k = 3 or 5): ConvTranspose2d(C, C, k, stride 2, padding (k-1)/2, output_padding 1, groups=C), the
+    FD_OP_DWT = 3,  /* depthwise TRANSPOSED k x k conv (k = 3 or 5): ConvTranspose2d(C, C, k, stride 2, padding (k-1)/2, output_padding 1, groups=C), the
                      * map-doubling unit of the DeConv decoder (models.py:89-99, 145-180).  cin == cout (fp32: a multiple of 4, 16-bit plans: of 8), stride = 2,
                      * upsample = 0, skip = -1, concat = 0; the output map is 2 x the input map in both directions.  conv_weight is torch's [cin][1][k][k].
                      * Inference plans only: fd_train_plan_create refuses a plan that contains one (FD_ERR_INVALID, the message names the layer). */
+    FD_OP_DWS = 4,  /* depthwise k x k conv (k = 3 or 5, stride 1, padding (k-1)/2) ON THE 2x PIXEL SHUFFLE of src's output, the unit of the ShuffleConv
+                     * decoder (models.py:296-333): with src = [B,h,w,4C] (NHWC) the layer's input is [B,2h,2w,C],
+                     * in[n][2y+i][2x+j][c] = src[n][y][x][4c+2i+j] (F.pixel_shuffle's channel order); the shuffled tensor is never stored.
+                     * cin == cout == C (16-bit plans: a multiple of 2), producer channels == 4C, stride = 1, upsample = 0, skip = -1, concat = 0.
+                     * conv_weight is torch's [C][1][k][k].  Inference plans only, as FD_OP_DWT. */
+    FD_OP_PWS = 5   /* pointwise cin -> 4 whose four outputs per pixel are written as the 2x2 quad of the fp32 network output:
+                     * y[n][0][2y+i][2x+j] = out[n][y][x][2i+j].  Only valid as the LAST layer, on a map of half the network's height and width;
+                     * cin % 4 == 0, cin <= 64, cout == 4, ksize = 1, stride = 1, upsample = 0, skip = -1, concat = 0.  Keeps fp32 weights in every
+                     * plan.  Inference plans only, as FD_OP_DWT. */
 };
 enum fd_act { FD_ACT_NONE = 0, FD_ACT_RELU = 1, FD_ACT_RELU6 = 2 };
 
@@ -70,7 +79,7 @@ enum fd_act { FD_ACT_NONE = 0, FD_ACT_RELU = 1, FD_ACT_RELU6 = 2 };
 typedef struct fd_layer_desc {
     int32_t op;       /* enum fd_op */
     int32_t cin;
-    int32_t cout;     /* == cin for FD_OP_DW / FD_OP_DWT */
+    int32_t cout;     /* == cin for FD_OP_DW / FD_OP_DWT / FD_OP_DWS */
     int32_t ksize;    /* 3 (stem, encoder dw), 5 (decoder dw), 1 (pw) */
     int32_t stride;   /* 1 or 2 (FD_OP_DWT: 2, the factor by which the map GROWS) */
     int32_t act;      /* enum fd_act */
