@@ -692,6 +692,16 @@ int fd_train_plan_unit_kernels(const fd_train_plan *plan, int32_t layer)
            (dw && L.fwd == TLayer::DwFwd::ROWS3 ? 32 : 0);
 }
 
+int fd_train_plan_dw_geometry(const fd_train_plan *plan, int32_t layer, int32_t *out, int32_t n_out)
+{
+    if (!plan || !out || n_out < 10 || layer < 0 || layer >= (int)plan->layers.size()) return -1;
+    const TLayer &L = plan->layers[layer];
+    if (L.d.op != FD_OP_DW) return -1;
+    const int32_t v[10] = {L.th, L.tw, L.bth, L.btw, L.d_th, L.d_tw, L.dw_n << L.cbq, L.pstr, L.bpstr, (int32_t)L.lds};
+    for (int k = 0; k < 10; ++k) out[k] = v[k];
+    return 10;
+}
+
 int fd_train_layer_tensor(const fd_train_plan *plan, int32_t layer, int32_t which, const void **device_ptr, int32_t *n, int32_t *h,
                           int32_t *w, int32_t *c)
 {

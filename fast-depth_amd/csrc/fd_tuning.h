@@ -56,6 +56,12 @@ int fd_train_plan_lds_rounding(const struct fd_train_plan *plan, int32_t layer);
  * fd_bn_bwd_finalize_block); bit 3: in the plan its backward runs on a row-walking depthwise kernel (fd_dw5_bwd_rows / fd_dw3_bwd_rows / fd_dw3s2_bwd_rows); bit 4: its forward runs on
  * fd_dw5_rows_train; bit 5: on fd_dw3_rows_fwd.  All of it is chosen at plan creation (valid right after it).  -1: bad arguments. */
 int fd_train_plan_unit_kernels(const struct fd_train_plan *plan, int32_t layer);
+/* Test hook (host only, reads the plan record): the tile geometry the plan chose for depthwise unit `layer`, so that a test of a tile-geometry tuning bit can
+ * show that the bit took effect -- out[0..9] = forward tile rows, forward tile columns (L.th, L.tw: what the LDS-tiled forward kernel would use; a unit whose
+ * forward runs on a row-walking / register-window kernel keeps them unused), backward-weights tile rows, columns (output space), backward-data tile rows,
+ * columns (input space), channels per block, forward patch pitch, backward patch pitch (LDS elements), forward dynamic LDS bytes.  Returns the number of
+ * values written (10); -1: bad arguments, n_out < 10 or not a depthwise unit. */
+int fd_train_plan_dw_geometry(const struct fd_train_plan *plan, int32_t layer, int32_t *out, int32_t n_out);
 /* Measurement hook (tools/gpu_round.sh, bench.py with FD_BENCH_FORCE_DIST=2): fd_train_backward_allreduce runs everything -- bucket ranges, event
  * hand-over to the communicator's stream, casts, the wait of the compute stream -- EXCEPT the ncclAllReduce calls.  On one rank this separates the
  * cost of the library's own machinery from RCCL's degenerate one-rank collective (a run of small copy / fill kernels).  Only valid on one rank. */

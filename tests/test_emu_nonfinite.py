@@ -10,9 +10,11 @@ finite depth map (or a finite loss for a diverged train step).  Three tiers:
     and a clean step afterwards that carries nothing of the poisoned one.
 """
 import ctypes
+import functools
 import math
 import os
 import sys
+import time
 from fractions import Fraction
 
 import numpy as np
@@ -293,20 +295,24 @@ INFER_CASES = [
 ]
 
 
-@pytest.mark.parametrize("name,plan,hw,dtype,flags", INFER_CASES, ids=[c[0] for c in INFER_CASES])
-def test_emulated_forward_propagates_nonfinite_like_reference(name, plan, hw, dtype, flags):
+def check_forward_propagates_nonfinite_like_reference(kind, name, plan, hw, dtype, flags):
     """A NaN / -NaN / +-Inf pixel at a corner, an edge or the centre of frame 0 ... 3, an all-NaN frame 4 and a clean frame 5, through an inference
     plan: exactly the reference's non-finite output pixels (no scrubbing by max / med3 / integer ReLU, no halo or padding lane 'masked' by a
-    multiplication with 0, which leaves a NaN), the reference's values elsewhere, and the clean frame bit-identical to an all-clean batch."""
+    multiplication with 0, which leaves a NaN), the reference's values elsewhere, and the clean frame bit-identical to an all-clean batch.
+    kind: "emu" (CPU emulator) or "hip" (the product library on the device)."""
+    t0 = time.time()
+    dev = torch.device("cpu" if kind == "emu" else "cuda")
     rot = sum(map(ord, name)) % 4
     m = small_model(plan[0], plan[1], seed=17).eval()
     x, clean, where = poisoned_batch(hw[0], hw[1], rot)
     ref = reference_forward(m, x)[:, 0]
-    p = harness.CPlan("emu", m, x, keep=False, dtype=dtype, flags=flags)
-    y = p.forward(x)[:, 0]
-    y_clean = p.forward(clean)[:, 0]
-    info = p.info()
-    p.close()
+    p = harness.CPlan(kind, m, x.to(dev), keep=False, dtype=dtype, flags=flags)
+    try:
+        y = p.forward(x.to(dev))[:, 0].cpu()
+        y_clean = p.forward(clean.to(dev))[:, 0].cpu()
+        info = p.info()
+    finally:
+        p.close()
     if flags == F.FD_TUNE_FORCE_GEMM16:
         assert sum(s.startswith("pw_gemm16") for s in info) == 18, info
     if flags == F.FD_TUNE_FORCE_UNIT_FUSION:
@@ -315,7 +321,16 @@ def test_emulated_forward_propagates_nonfinite_like_reference(name, plan, hw, dt
         assert any("evaluated in the epilogue" in s for s in info), info
     if dtype != torch.float32 and flags == 0 and plan is RAGGED:
         assert any(s.startswith("dw5_rows<") for s in info), info          # the packed-pair 5x5 kernel and its packed ReLU
+    fin = torch.isfinite(ref)
+    print("FORMS %s forward_propagates_nonfinite[%s] finite_pixels_rel_err=%.3g tol=%g nonfinite_mask_mismatches=%d" % (
+        kind, name, float((y.double() - ref)[fin].abs().max()) / float(ref[fin].abs().max()), TOLS[dtype], int((torch.isfinite(y) != fin).sum())), end="")
     check_nonfinite_forward(y, y_clean, ref, where, TOLS[dtype])
+    print(" wall=%.2fs" % (time.time() - t0))
+
+
+@pytest.mark.parametrize("name,plan,hw,dtype,flags", INFER_CASES, ids=[c[0] for c in INFER_CASES])
+def test_emulated_forward_propagates_nonfinite_like_reference(name, plan, hw, dtype, flags):
+    check_forward_propagates_nonfinite_like_reference("emu", name, plan, hw, dtype, flags)
 
 
 # ---- train step -------------------------------------------------------------------------------------------------------------------------
@@ -438,22 +453,40 @@ TRAIN_CASES = [
 ]
 
 
-@pytest.mark.parametrize("name,dtype,flags", TRAIN_CASES, ids=[c[0] for c in TRAIN_CASES])
-def test_emulated_train_step_with_nan_pixel_like_reference(name, dtype, flags):
-    """A NaN pixel in frame 0 of a train step: the batch statistics of the stem are NaN, so -- as in the reference -- every later unit's are,
-    the prediction and the loss are NaN, dLoss/dpred is torch's sign(NaN) = 0, num_batches_tracked still counts the step, and the same set of
-    gradient tensors carries a non-finite entry.  Nothing of it survives into the next (clean) step of the same plan."""
+@functools.lru_cache(maxsize=None)
+def nan_pixel_step_case():
+    """(module, clean x, target, x with a NaN pixel in frame 0, fp64 reference of the poisoned step): computed once, shared by the cases of both
+    tiers, never modified (a TrainStep works on private copies of the parameters)."""
     m = small_model(TINY[0], TINY[1], seed=3).train()
     g = torch.Generator().manual_seed(9)
     x = torch.rand(2, 3, 64, 64, generator=g)
     target = 2.0 + torch.rand(2, 1, 64, 64, generator=g)
     xp = x.clone()
     xp[0, :, 21, 40] = float("nan")
-    ref = reference_train_step(m, xp, target)
-    step = TrainStep("emu", m, xp, dtype, flags)
-    got = step.run(xp, target)
-    n_bad, n = check_nonfinite_train_step(got, ref)
-    assert n == 114 and n_bad > 0
-    if flags == 0:                     # (the clean step afterwards: once per storage type)
-        check_clean_step_after_poison("emu", m, x, target, dtype, flags, step)
-    step.close()
+    return m, x, target, xp, reference_train_step(m, xp, target)
+
+
+def check_train_step_with_nan_pixel_like_reference(kind, name, dtype, flags):
+    """A NaN pixel in frame 0 of a train step: the batch statistics of the stem are NaN, so -- as in the reference -- every later unit's are,
+    the prediction and the loss are NaN, dLoss/dpred is torch's sign(NaN) = 0, num_batches_tracked still counts the step, and the same set of
+    gradient tensors carries a non-finite entry.  Nothing of it survives into the next (clean) step of the same plan.
+    kind: "emu" (CPU emulator) or "hip" (the product library on the device)."""
+    t0 = time.time()
+    dev = torch.device("cpu" if kind == "emu" else "cuda")
+    m, x, target, xp, ref = nan_pixel_step_case()
+    step = TrainStep(kind, m, xp.to(dev), dtype, flags)
+    try:
+        got = step.run(xp.to(dev), target)
+        n_bad, n = check_nonfinite_train_step(got, ref)
+        print("FORMS %s train_step_with_nan_pixel[%s] gradient_tensors_with_nonfinite=%d/%d (the reference's set exactly)" % (kind, name, n_bad, n), end="")
+        assert n == 114 and n_bad > 0
+        if flags == 0:                     # (the clean step afterwards: once per storage type)
+            check_clean_step_after_poison(kind, m, x.to(dev), target, dtype, flags, step)
+        print(" wall=%.2fs (the shared fp64 reference is computed by the first case)" % (time.time() - t0))
+    finally:
+        step.close()
+
+
+@pytest.mark.parametrize("name,dtype,flags", TRAIN_CASES, ids=[c[0] for c in TRAIN_CASES])
+def test_emulated_train_step_with_nan_pixel_like_reference(name, dtype, flags):
+    check_train_step_with_nan_pixel_like_reference("emu", name, dtype, flags)
