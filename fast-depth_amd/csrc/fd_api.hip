@@ -13,6 +13,7 @@
 #include "fd_kernels_dw5p.h"
 #include "fd_kernels_dwt.h"
 #include "fd_kernels_dws.h"
+#include "fd_kernels_dwb.h"
 #include "../../include/fastdepth_hip.h"
 #include "fd_tuning.h"
 
@@ -115,7 +116,7 @@ int fd_plan_pack_weights(fd_plan *plan, const fd_layer_params *params, int32_t n
                                reinterpret_cast<float *>(plan->ws + L.w_off), bptr, L.d.cout, inner, transpose, pitch);
         int rc = check_launch("fd_pack_fold");
         if (rc) return rc;
-        if (L.dwt || L.dws || L.pws) {                       // transposed and pixel-shuffle layers: the bias folded in fp64 (fd_kernels_dwt.h)
+        if (L.dwt || L.dws || L.pws || L.dwb || L.pwb) {     // transposed, pixel-shuffle and bilinear layers: the bias folded in fp64 (fd_kernels_dwt.h)
             hipLaunchKernelGGL(fd_dwt_fold_bias, dim3(ceil_div(L.d.cout, 256)), dim3(256), 0, s, q.bn_weight, q.bn_bias, q.bn_mean, q.bn_var, bn_eps, bptr, L.d.cout);
             rc = check_launch("fd_dwt_fold_bias");
             if (rc) return rc;

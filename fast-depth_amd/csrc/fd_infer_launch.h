@@ -91,6 +91,15 @@ int launch_dws(const Layer &L, const T *in, const float *wp, const float *bias, 
     return check_launch("fd_dws_rows");
 }
 
+// depthwise conv on the bilinear x2 of the producer's output, register-window kernel (fd_kernels_dwb.h); in_h x in_w is the upsampled map
+template <typename T, int ACT>
+int launch_dwb(const Layer &L, const T *in, const float *wp, const float *bias, T *out, hipStream_t s)
+{
+    if (L.d.ksize == 5) FD_LAUNCH((fd_dwb_rows<T, 5, ACT>), L.grid, dim3(256), 0, s, in, wp, bias, out, L.in_h / 2, L.in_w / 2, L.d.cin, L.th);
+    else FD_LAUNCH((fd_dwb_rows<T, 3, ACT>), L.grid, dim3(256), 0, s, in, wp, bias, out, L.in_h / 2, L.in_w / 2, L.d.cin, L.th);
+    return check_launch("fd_dwb_rows");
+}
+
 template <int ACT>
 int launch_pw(const fd_plan *plan, const Layer &L, const float *A, const float *wp, const float *bias, float *out, long M, hipStream_t s)
 {
@@ -246,6 +255,10 @@ int launch_layer(const fd_plan *p, const Layer &L, const float *x, float *y, hip
     case FD_OP_PWS:
         FD_LAUNCH((fd_head_shuffle<T, ACT>), L.grid, dim3(256), 0, s, in, wpf, bias, y, (long)p->B * L.out_h * L.out_w, L.out_h, L.out_w, L.d.cin);
         return check_launch("fd_head_shuffle");
+    case FD_OP_DWB: return launch_dwb<T, ACT>(L, in, wpf, bias, out, s);
+    case FD_OP_PWB:                                          // in_h x in_w is the half-size source map
+        FD_LAUNCH((fd_head_bilinear<T, ACT>), L.grid, dim3(256), 0, s, in, wpf, bias, y, L.in_h, L.in_w, L.d.cin);
+        return check_launch("fd_head_bilinear");
     case FD_OP_PW:
         if (L.head) {
             const int h = L.d.upsample ? L.in_h / 2 : L.in_h, w = L.d.upsample ? L.in_w / 2 : L.in_w;

@@ -29,9 +29,12 @@ int plan_layers(fd_plan *p, const fd_layer_desc *layers, size_t *woff_out)
             if (src_c + p->layers[d.skip].d.cout != d.cin || src_c % 4) FD_BAD("layer %d: concat of %d + %d channels does not give cin %d", i, src_c, p->layers[d.skip].d.cout, d.cin);
         } else if (d.op == FD_OP_DWS) {                        // reads through the 2x pixel shuffle: a quarter of the channels, twice the map
             if (d.src < 0 || src_c != 4 * d.cin) FD_BAD("layer %d: pixel-shuffle depthwise needs 4 * cin (%d) == producer channels %d", i, d.cin, src_c);
+        } else if (d.op == FD_OP_DWB) {                        // reads through the bilinear x2: the same channels, twice the map
+            if (d.src < 0 || src_c != d.cin) FD_BAD("layer %d: bilinear depthwise (FD_OP_DWB) needs cin (%d) == producer channels %d", i, d.cin, src_c);
         } else if (src_c != d.cin) FD_BAD("layer %d: cin %d != producer channels %d", i, d.cin, src_c);
-        L.in_h = (d.upsample || d.op == FD_OP_DWS) ? 2 * src_h : src_h;
-        L.in_w = (d.upsample || d.op == FD_OP_DWS) ? 2 * src_w : src_w;
+        const bool doubled_in = d.upsample || d.op == FD_OP_DWS || d.op == FD_OP_DWB;     // (FD_OP_PWB: in_h x in_w is its half-size SOURCE map)
+        L.in_h = doubled_in ? 2 * src_h : src_h;
+        L.in_w = doubled_in ? 2 * src_w : src_w;
         if (d.skip >= 0) {
             const Layer &S = p->layers[d.skip];
             if (!d.upsample) FD_BAD("layer %d: skip without upsample is not part of this path", i);
@@ -156,6 +159,34 @@ int plan_layers(fd_plan *p, const fd_layer_desc *layers, size_t *woff_out)
             L.out_h = L.in_h; L.out_w = L.in_w;
             L.w_bytes = (size_t)d.cin * 4 * 4; L.w_elems = (size_t)d.cin * 4;
             L.grid = dim3(ceil_div((long)batch * L.out_h * L.out_w, 256));
+            break;
+        case FD_OP_DWB: {
+            // depthwise conv, stride 1, on the bilinear x2 of the producer's output (fd_kernels_dwb.h): in_h x in_w is the upsampled map
+            if (d.cin != d.cout || (d.ksize != 3 && d.ksize != 5) || d.stride != 1 || d.upsample || d.skip >= 0 || concat || d.cin % 2)
+                FD_BAD("layer %d: bilinear depthwise (FD_OP_DWB) needs cin==cout (a multiple of 2), k in {3,5}, stride 1, no upsample / skip / concat", i);
+            L.dwb = true;
+            L.out_h = L.in_h; L.out_w = L.in_w;
+            // band height (SOURCE rows): halved until the grid has >= ~4 workgroups per CU, as for fd_dwt_rows; a band re-reads 2 R halo rows (k = 5: 4, k = 3: 2)
+            const int sh = L.in_h / 2, sw = L.in_w / 2;
+            const int gx = ceil_div((long)sw * (d.cin / 2), 256);
+            int th = sh;
+            while (th > 4 && (long)gx * ceil_div(sh, th) * batch < 1024) th = (th + 1) / 2;
+            L.th = th;
+            L.grid = dim3(gx, ceil_div(sh, th), batch);
+            L.lds = 0;
+            L.w_bytes = (size_t)d.ksize * d.ksize * d.cin * 4; L.w_elems = (size_t)d.ksize * d.ksize * d.cin;
+            break;
+        }
+        case FD_OP_PWB:
+            // pointwise cin -> 1 evaluated on the half-size map, interpolated (bilinear x2) into the fp32 network output (fd_kernels_dwb.h); fp32 weights [cin] in every plan
+            if (d.src < 0 || d.ksize != 1 || d.stride != 1 || d.cin % 4 || d.cin > 64 || d.cout != 1 || d.upsample || d.skip >= 0 || concat)
+                FD_BAD("layer %d: bilinear head (FD_OP_PWB) needs k=1 stride=1, cin%%4==0, cin<=64, cout==1, no upsample / skip / concat", i);
+            if (i != n_layers - 1) FD_BAD("layer %d: the bilinear head (FD_OP_PWB) is only valid as the last layer", i);
+            if (batch > 65535) FD_BAD("layer %d: the bilinear head (FD_OP_PWB) takes at most 65535 images per launch", i);
+            L.pwb = true;
+            L.out_h = 2 * L.in_h; L.out_w = 2 * L.in_w;
+            L.w_bytes = (size_t)d.cin * 4; L.w_elems = (size_t)d.cin;
+            L.grid = dim3(ceil_div(L.in_w, FD_HEADB_TILE), ceil_div(L.in_h, FD_HEADB_TILE), batch);
             break;
         case FD_OP_PW:
             if (d.src < 0 || d.ksize != 1 || d.stride != 1 || d.cin % 4) FD_BAD("layer %d: pointwise needs k=1 stride=1 cin%%4==0", i);
@@ -425,15 +456,17 @@ void plan_describe(fd_plan *p)
         const fd_layer_desc &d = L.d;
         const int c_src = L.csplit ? L.csplit : d.cin, c_skip = L.csplit ? d.cin - L.csplit : d.cin;
         // (a pixel-shuffle depthwise layer reads in_h/2 x in_w/2 pixels of 4 cin channels: the same element count as its shuffled input map)
-        const double src_elems = (double)batch * (d.upsample ? (L.in_h / 2) * (L.in_w / 2) : L.in_h * L.in_w) * c_src;
+        // (a bilinear depthwise layer reads the in_h/2 x in_w/2 source map once; the bilinear head's in_h x in_w IS its source map)
+        const double src_elems = (double)batch * ((d.upsample || d.op == FD_OP_DWB) ? (L.in_h / 2) * (L.in_w / 2) : L.in_h * L.in_w) * c_src;
         const double skip_elems = d.skip >= 0 ? (double)batch * L.in_h * L.in_w * c_skip : 0.0;
         const double out_elems = (double)batch * L.out_h * L.out_w * d.cout;
         const double in_esz = d.src < 0 ? 4.0 : (double)esz, out_esz = L.to_output ? 4.0 : (double)esz;   // network input / output stay fp32
         L.alg_bytes = (src_elems + skip_elems) * in_esz + out_elems * out_esz + (double)L.w_elems * (L.pw_packed_t ? esz : 4) + 2.0 * d.cout * 4;
         p->alg_bytes += L.alg_bytes;
         // (transposed depthwise, polyphase: k^2 / 4 multiply-adds per output)
-        const double taps = d.op == FD_OP_STEM ? 27.0 : ((d.op == FD_OP_DW || d.op == FD_OP_DWS) ? (double)d.ksize * d.ksize : (d.op == FD_OP_DWT ? d.ksize * d.ksize / 4.0 : (double)d.cin));
-        const double mac_px = L.head && d.upsample ? (double)L.out_h * L.out_w : (double)L.out_h * L.out_w;
+        // (bilinear layers: the interpolation is not counted; the bilinear head forms its dot products on the half-size map)
+        const double taps = d.op == FD_OP_STEM ? 27.0 : ((d.op == FD_OP_DW || d.op == FD_OP_DWS || d.op == FD_OP_DWB) ? (double)d.ksize * d.ksize : (d.op == FD_OP_DWT ? d.ksize * d.ksize / 4.0 : (double)d.cin));
+        const double mac_px = L.pwb ? (double)L.in_h * L.in_w : (double)L.out_h * L.out_w;
         L.alg_flops = 2.0 * batch * mac_px * d.cout * taps;
         p->alg_flops += L.alg_flops;
         char buf[256];
@@ -457,6 +490,12 @@ void plan_describe(fd_plan *p)
                      d.ksize, dtype == FD_F32 ? 1 : 2, L.th, L.grid.x, L.grid.y, L.grid.z);
         else if (d.op == FD_OP_PWS)
             snprintf(buf, sizeof buf, "head_shuffle<%d -> 4, written as the 2x2 quads of the network output> grid=%u", d.cin, L.grid.x);
+        else if (d.op == FD_OP_DWB)
+            snprintf(buf, sizeof buf, "dwb_rows<k%d s1 on the bilinear x2 of the producer, 2 channels per work-item> %d source rows per band, grid=%ux%ux%u, no LDS",
+                     d.ksize, L.th, L.grid.x, L.grid.y, L.grid.z);
+        else if (d.op == FD_OP_PWB)
+            snprintf(buf, sizeof buf, "head_bilinear<%d -> 1 on the %dx%d map, interpolated x2 into the network output> 16x16 source tiles, grid=%ux%ux%u", d.cin, L.in_h, L.in_w,
+                     L.grid.x, L.grid.y, L.grid.z);
         else if (d.op == FD_OP_DW && L.dw5_cl)
             snprintf(buf, sizeof buf, "dw5_rows<k5 s1 mode2, pixel pairs + dot2, %d channel lanes per strip> bands of %d rows, %d strip groups, %d channels per block, grid=%ux%ux%u, no LDS",
                      L.dw5_cl, L.dw5_bh, L.dw5_groups, L.dw5_cbs, L.grid.x, L.grid.y, L.grid.z);
@@ -484,6 +523,8 @@ void plan_describe(fd_plan *p)
         else if (d.op == FD_OP_DWT) snprintf(buf, sizeof buf, "fd_dwt_rows<%s, %d, %d>", tn, d.ksize, d.act);
         else if (d.op == FD_OP_DWS) snprintf(buf, sizeof buf, "fd_dws_rows<%s, %d, %d>", tn, d.ksize, d.act);
         else if (d.op == FD_OP_PWS) snprintf(buf, sizeof buf, "fd_head_shuffle<%s, %d>", tn, d.act);
+        else if (d.op == FD_OP_DWB) snprintf(buf, sizeof buf, "fd_dwb_rows<%s, %d, %d>", tn, d.ksize, d.act);
+        else if (d.op == FD_OP_PWB) snprintf(buf, sizeof buf, "fd_head_bilinear<%s, %d>", tn, d.act);
         else if (d.op == FD_OP_DW && L.dw5_cl) snprintf(buf, sizeof buf, "fd_dw5_rows<%s, %d, %d>", tn, d.act, L.dw5_cl);
         else if (d.op == FD_OP_DW && L.dw_rows) snprintf(buf, sizeof buf, "fd_dw3_rows%s<%s, %d, %d>", L.dw_rows8 ? "8" : "", tn, d.stride, d.act);
         else if (d.op == FD_OP_DW) snprintf(buf, sizeof buf, "fd_dwconv<%s, %d, %d, %d, %d, %d>", tn, d.ksize, d.stride, L.mode, d.act, L.dw_n);

@@ -76,6 +76,8 @@ struct Layer {
     bool dwt = false;            // transposed depthwise layer (FD_OP_DWT): the polyphase register-window kernel fd_dwt_rows, th input rows per band
     bool dws = false;            // depthwise layer on the pixel shuffle of its producer (FD_OP_DWS): fd_dws_rows, th source rows per band
     bool pws = false;            // pointwise cin -> 4 written through the pixel shuffle as the network output (FD_OP_PWS): fd_head_shuffle
+    bool dwb = false;            // depthwise layer on the bilinear x2 of its producer (FD_OP_DWB): fd_dwb_rows, th source rows per band
+    bool pwb = false;            // pointwise cin -> 1 evaluated on the half-size map and interpolated into the network output (FD_OP_PWB): fd_head_bilinear
     // stem
     int chunk = 0;
     // pw

@@ -375,6 +375,8 @@ int fd_train_plan_create(const fd_layer_desc *layers, int32_t n_layers, int32_t 
         if (d.op == FD_OP_DWT) FD_BAD("layer %d: transposed depthwise units (FD_OP_DWT) run in inference plans only; their train step is not implemented", i);
         if (d.op == FD_OP_DWS || d.op == FD_OP_PWS)
             FD_BAD("layer %d: pixel-shuffle units (%s) run in inference plans only; their train step is not implemented", i, d.op == FD_OP_DWS ? "FD_OP_DWS" : "FD_OP_PWS");
+        if (d.op == FD_OP_DWB || d.op == FD_OP_PWB)
+            FD_BAD("layer %d: bilinear-upsampling units (%s) run in inference plans only; their train step is not implemented", i, d.op == FD_OP_DWB ? "FD_OP_DWB" : "FD_OP_PWB");
         if (d.act != FD_ACT_RELU && d.act != FD_ACT_RELU6) FD_BAD("layer %d: train mode needs ReLU or ReLU6", i);
         int src_h, src_w, src_c;
         if (d.src < 0) { src_h = height; src_w = width; src_c = 3; }

@@ -9,6 +9,8 @@ their own: they become `upsample` / `skip` attributes of the layer that consumes
 (`decoder.convt1..5`, `decoder.convf`) upsamples nowhere: its depthwise transposed convolutions are layers of their own kind (FD_OP_DWT).
 The ShuffleConv decoder (`decoder.conv1..4`) puts a 2x pixel shuffle before each unit and after the last: its depthwise layers read through the
 shuffle (FD_OP_DWS) and its last pointwise layer writes the network output through it (FD_OP_PWS).
+The BLConv decoder (`decoder.conv1..6`, class attribute `_fd_upsample = "bilinear"`) puts a bilinear x2 after conv1..conv5: the depthwise layers
+of conv2..conv5 interpolate their producer's output themselves (FD_OP_DWB), and conv6 is evaluated before the last interpolation (FD_OP_PWB).
 """
 import torch.nn as nn
 
@@ -62,11 +64,11 @@ class Layer:
     __slots__ = ("conv", "bn", "desc", "name")
 
     def __init__(self, name, conv, bn, act, src, upsample=0, skip=-1, concat=0, op=None):
-        # op: told by the walk where the module alone does not say it (the pixel-shuffle layers are plain depthwise / pointwise convolutions)
+        # op: told by the walk where the module alone does not say it (the pixel-shuffle and bilinear layers are plain depthwise / pointwise convolutions)
         k = conv.kernel_size[0]
         if op is not None:
-            want = (conv.groups == conv.in_channels == conv.out_channels and k in (3, 5)) if op == capi.FD_OP_DWS else (conv.groups == 1 and k == 1)
-            if op not in (capi.FD_OP_DWS, capi.FD_OP_PWS) or not want or conv.stride != (1, 1):
+            want = (conv.groups == conv.in_channels == conv.out_channels and k in (3, 5)) if op in (capi.FD_OP_DWS, capi.FD_OP_DWB) else (conv.groups == 1 and k == 1)
+            if op not in (capi.FD_OP_DWS, capi.FD_OP_PWS, capi.FD_OP_DWB, capi.FD_OP_PWB) or not want or conv.stride != (1, 1):
                 raise capi.FastDepthError("%s: conv %r cannot run as op %r" % (name, conv, op))
         elif isinstance(conv, nn.ConvTranspose2d):     # (validated by _units)
             op = capi.FD_OP_DWT
@@ -108,6 +110,19 @@ def _layers_of_plain(model):
                 raise capi.FastDepthError("decoder.conv%d: expected a (depthwise, pointwise) pair, got %d units" % (j, len(units)))
             for q, (conv, bn, act) in enumerate(units):
                 op = capi.FD_OP_DWS if q == 0 else (capi.FD_OP_PWS if j == 4 else None)
+                layers.append(Layer("decoder.conv%d.%d" % (j, q), conv, bn, act, src, op=op))
+                src = len(layers) - 1
+        return layers
+    if getattr(type(model.decoder), "_fd_upsample", "nearest") == "bilinear":
+        # BLConv decoder (reference models.py:272-294): NNConv's modules with a bilinear x2 after conv1..conv5.  The interpolation is arithmetic, not
+        # an index map: the depthwise layer that follows one does it in registers (FD_OP_DWB), and the last one, which does not commute with conv6's
+        # ReLU only, moves behind conv6's affine part (FD_OP_PWB).  conv1.0 sees the encoder output as it is.  Nothing carries `upsample`
+        for j in range(1, 7):
+            units = _units(getattr(model.decoder, "conv%d" % j))
+            if len(units) != (2 if j <= 5 else 1):
+                raise capi.FastDepthError("decoder.conv%d: expected %s, got %d units" % (j, "a (depthwise, pointwise) pair" if j <= 5 else "one pointwise unit", len(units)))
+            for q, (conv, bn, act) in enumerate(units):
+                op = capi.FD_OP_PWB if j == 6 else (capi.FD_OP_DWB if q == 0 and j >= 2 else None)
                 layers.append(Layer("decoder.conv%d.%d" % (j, q), conv, bn, act, src, op=op))
                 src = len(layers) - 1
         return layers

@@ -25,7 +25,7 @@ import torch.nn as nn
 
 import imagenet.mobilenet as _mobilenet
 
-__all__ = ["MobileNetSkipAdd", "MobileNetSkipConcat", "MobileNet", "NNConv", "DeConv", "ShuffleConv", "choose_decoder", "depthwise", "pointwise", "weights_init", "PRUNED_CHANNELS"]
+__all__ = ["MobileNetSkipAdd", "MobileNetSkipConcat", "MobileNet", "NNConv", "BLConv", "DeConv", "ShuffleConv", "choose_decoder", "depthwise", "pointwise", "weights_init", "PRUNED_CHANNELS"]
 
 # Channel plan of `mobilenet-nnconv5dw-skipadd-pruned`, reconstructed from the reference's TVM tuning
 # log (tvm_compile/tuning/tx2-gpu.mobilenet-nnconv5dw-skipadd-pruned.trials=2000.stop=600.log:1-38,
@@ -132,6 +132,24 @@ class NNConv(nn.Module):
         self.conv6 = pointwise(width, 1)
 
 
+class BLConv(NNConv):
+    """Bilinear-upsampling decoder, depthwise-separable form (reference models.py:272-294 with dw=True): NNConv's module tree
+    (conv1..conv6, the same 228 keys of the whole model), whose forward puts F.interpolate(scale_factor=2, mode='bilinear',
+    align_corners=False) where NNConv puts the nearest x2.  Parameter container only (the HIP engine executes it as part of
+    `MobileNet`: conv2..conv5's depthwise layers interpolate their producer's output in registers on fd_dwb_rows, conv6 is evaluated
+    on the half-size map and interpolated into the output on fd_head_bilinear).  Subclass of NNConv as in the reference, so that a
+    pickled reference module resolves `models.BLConv` with the same method resolution order.  The dense variant (dw=False) is outside
+    this package's kernels."""
+
+    _fd_upsample = "bilinear"                # class attribute: survives unpickling of reference-format checkpoints
+
+    def __init__(self, kernel_size, dw):
+        if not dw:
+            raise NotImplementedError("fast-depth_amd implements the depthwise-separable decoders ('blconv5dw', 'blconv3dw'); "
+                                      "the dense BLConv decoder is not on the accelerated path")
+        super().__init__(kernel_size, dw)
+
+
 class DeConv(nn.Module):
     """Transposed-convolution decoder, depthwise-separable form (reference models.py:145-180 with dw=True):
     convt1..convt5 = Sequential(depthwise_transposed(C, k), pointwise(C, C/2)) for C = 1024..64, convf = pointwise(32, 1).  Every
@@ -175,8 +193,11 @@ def choose_decoder(decoder):
         model = DeConv(int(decoder[6]), True)
     elif decoder in ('shuffle5dw', 'shuffle3dw'):
         model = ShuffleConv(int(decoder[7]), True)
+    elif decoder in ('blconv5dw', 'blconv3dw'):
+        model = BLConv(int(decoder[6]), True)
     else:
-        raise NotImplementedError("decoder {!r}: only 'nnconv5dw' / 'nnconv3dw' / 'deconv5dw' / 'deconv3dw' / 'shuffle5dw' / 'shuffle3dw' are built by fast-depth_amd "
+        raise NotImplementedError("decoder {!r}: only 'nnconv5dw' / 'nnconv3dw' / 'deconv5dw' / 'deconv3dw' / 'shuffle5dw' / 'shuffle3dw' / 'blconv5dw' / 'blconv3dw' "
+                                  "are built by fast-depth_amd "
                                   "(SURVEY.md 8(f) row f-3)".format(decoder))
     model.apply(weights_init)
     return model
@@ -186,7 +207,7 @@ class MobileNet(_HipForward):
     """MobileNet-v1 encoder + decoder WITHOUT skip connections -- `MobileNet(decoder, output_size, in_channels=3,
     pretrained=True)` as in reference models.py:420-460 (runs on the same kernels as
     MobileNetSkipAdd, with `skip = -1` everywhere).  Attribute tree and state_dict keys follow the reference:
-    `mobilenet.0 .. mobilenet.13`, `decoder.conv1 .. decoder.conv6` (NNConv) or `decoder.convt1 .. decoder.convt5`, `decoder.convf` (DeConv)
+    `mobilenet.0 .. mobilenet.13`, `decoder.conv1 .. decoder.conv6` (NNConv, BLConv) or `decoder.convt1 .. decoder.convt5`, `decoder.convf` (DeConv)
     or `decoder.conv1 .. decoder.conv4` (ShuffleConv)."""
 
     def __init__(self, decoder, output_size, in_channels=3, pretrained=True):

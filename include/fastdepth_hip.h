@@ -57,9 +57,20 @@ enum fd_op {
                      * in[n][2y+i][2x+j][c] = src[n][y][x][4c+2i+j] (F.pixel_shuffle's channel order); the shuffled tensor is never stored.
                      * cin == cout == C (16-bit plans: a multiple of 2), producer channels == 4C, stride = 1, upsample = 0, skip = -1, concat = 0.
                      * conv_weight is torch's [C][1][k][k].  Inference plans only, as FD_OP_DWT. */
-    FD_OP_PWS = 5   /* pointwise cin -> 4 whose four outputs per pixel are written as the 2x2 quad of the fp32 network output:
+    FD_OP_PWS = 5,  /* pointwise cin -> 4 whose four outputs per pixel are written as the 2x2 quad of the fp32 network output:
                      * y[n][0][2y+i][2x+j] = out[n][y][x][2i+j].  Only valid as the LAST layer, on a map of half the network's height and width;
                      * cin % 4 == 0, cin <= 64, cout == 4, ksize = 1, stride = 1, upsample = 0, skip = -1, concat = 0.  Keeps fp32 weights in every
+                     * plan.  Inference plans only, as FD_OP_DWT. */
+    FD_OP_DWB = 6,  /* depthwise k x k conv (k = 3 or 5, stride 1, padding (k-1)/2) ON THE BILINEAR x2 of src's output, the unit of the BLConv decoder
+                     * (models.py:272-294): with src = [B,h,w,C] (NHWC) the layer's input is F.interpolate(src, scale_factor=2, mode='bilinear',
+                     * align_corners=False) = [B,2h,2w,C], separable weights 1/4 and 3/4 on a clamped source index; the convolution zero-pads the
+                     * UPSAMPLED map; the upsampled tensor is never stored.  cin == cout == C (a multiple of 2), producer channels == C, stride = 1,
+                     * upsample = 0, skip = -1, concat = 0; the output map is 2 x the source map.  conv_weight is torch's [C][1][k][k].
+                     * Inference plans only, as FD_OP_DWT. */
+    FD_OP_PWB = 7   /* pointwise cin -> 1 + BatchNorm evaluated on src's map, then interpolated (bilinear x2, as FD_OP_DWB), activated and written as the
+                     * fp32 network output: y = act(up(s pw(src) + t)), which equals act(s pw(up(src)) + t) because the affine part commutes with
+                     * an interpolation whose weights sum to 1.  Only valid as the LAST layer, on a map of half the network's height and width;
+                     * cin % 4 == 0, cin <= 64, cout == 1, ksize = 1, stride = 1, upsample = 0, skip = -1, concat = 0.  Keeps fp32 weights in every
                      * plan.  Inference plans only, as FD_OP_DWT. */
 };
 enum fd_act { FD_ACT_NONE = 0, FD_ACT_RELU = 1, FD_ACT_RELU6 = 2 };
@@ -79,7 +90,7 @@ enum fd_act { FD_ACT_NONE = 0, FD_ACT_RELU = 1, FD_ACT_RELU6 = 2 };
 typedef struct fd_layer_desc {
     int32_t op;       /* enum fd_op */
     int32_t cin;
-    int32_t cout;     /* == cin for FD_OP_DW / FD_OP_DWT / FD_OP_DWS */
+    int32_t cout;     /* == cin for FD_OP_DW / FD_OP_DWT / FD_OP_DWS / FD_OP_DWB */
     int32_t ksize;    /* 3 (stem, encoder dw), 5 (decoder dw), 1 (pw) */
     int32_t stride;   /* 1 or 2 (FD_OP_DWT: 2, the factor by which the map GROWS) */
     int32_t act;      /* enum fd_act */
