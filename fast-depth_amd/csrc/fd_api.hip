@@ -138,6 +138,9 @@ int fd_forward(fd_plan *plan, const void *x_nchw, void *y, void *stream)
 {
     if (!plan || !x_nchw || !y) return fail(FD_ERR_INVALID, "null argument");
     if (!plan->ws || !plan->packed) return fail(FD_ERR_STATE, "plan needs a bound workspace and packed weights");
+    // fd_stem3x3s2 stages x with 16-byte row loads; the head kernels write y as 8-byte pixel pairs
+    if (misaligned(x_nchw, 16)) return fail(FD_ERR_INVALID, "x must be 16-byte aligned");
+    if (misaligned(y, 8)) return fail(FD_ERR_INVALID, "y must be 8-byte aligned");
     hipStream_t s = static_cast<hipStream_t>(stream);
     for (size_t i = 0; i < plan->layers.size(); ++i) {
         const Layer &L = plan->layers[i];

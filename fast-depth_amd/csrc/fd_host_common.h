@@ -59,7 +59,8 @@ int fail(int code, const char *fmt, ...)
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
-
+// the caller-pointer contract of include/fastdepth_hip.h: refused before anything is launched
+inline bool misaligned(const void *p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a != 0; }
 
 int check_launch(const char *what)
 {

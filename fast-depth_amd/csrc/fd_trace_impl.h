@@ -41,6 +41,8 @@ int fd_forward_timed(fd_plan *plan, const void *x_nchw, void *y, void *stream, f
     if (!plan || !x_nchw || !y || !ms_per_layer) return fail(FD_ERR_INVALID, "null argument");
     if (!plan->ws || !plan->packed) return fail(FD_ERR_STATE, "plan needs a bound workspace and packed weights");
     if (n_layers != (int)plan->layers.size()) return fail(FD_ERR_INVALID, "expected room for %zu layer timings", plan->layers.size());
+    if (misaligned(x_nchw, 16)) return fail(FD_ERR_INVALID, "x must be 16-byte aligned");
+    if (misaligned(y, 8)) return fail(FD_ERR_INVALID, "y must be 8-byte aligned");
 #ifdef FD_EMU
     for (int i = 0; i < n_layers; ++i) ms_per_layer[i] = 0.0f;
     return fd_forward(plan, x_nchw, y, stream);

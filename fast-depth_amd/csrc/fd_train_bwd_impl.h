@@ -480,6 +480,9 @@ int fd_train_backward_range(fd_train_plan *plan, const fd_layer_params *params, 
     if (from_layer < to_layer || from_layer >= n_layers || to_layer < 0) return fail(FD_ERR_INVALID, "bad layer range %d..%d", from_layer, to_layer);
     for (int i = 0; i < n_layers; ++i)
         if (!grads[i].conv_weight || !grads[i].bn_weight || !grads[i].bn_bias) return fail(FD_ERR_INVALID, "layer %d: null gradient pointer", i);
+    // the backward kernels read the live conv weights with 16-byte loads; dy and every gradient tensor are accessed element by element
+    for (int i = 0; i < n_layers; ++i)
+        if (misaligned(params[i].conv_weight, 16)) return fail(FD_ERR_INVALID, "layer %d: conv_weight must be 16-byte aligned", i);
     return plan->dtype == FD_BF16 ? train_backward_t<fd_bf16>(plan, params, grads, n_layers, dy, from_layer, to_layer, stream)
                                   : train_backward_t<float>(plan, params, grads, n_layers, dy, from_layer, to_layer, stream);
 }

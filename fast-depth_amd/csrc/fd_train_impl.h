@@ -672,6 +672,12 @@ int fd_train_forward(fd_train_plan *plan, const fd_layer_params *params, int32_t
     if (!plan || !params || !x_nchw || !y) return fail(FD_ERR_INVALID, "null argument");
     if (!plan->ws) return fail(FD_ERR_STATE, "bind a workspace first");
     if (n_layers != (int)plan->layers.size()) return fail(FD_ERR_INVALID, "expected %zu layer parameter sets", plan->layers.size());
+    // fd_stem_stage_band stages x with 16-byte row loads (and the stem's weight gradient re-reads it so in fd_train_backward); fd_head_apply_f32 writes y as
+    // 8-byte pixel pairs; fd_head_train and the pointwise GEMMs read the live conv weights with 16-byte loads
+    if (misaligned(x_nchw, 16)) return fail(FD_ERR_INVALID, "x must be 16-byte aligned");
+    if (misaligned(y, 8)) return fail(FD_ERR_INVALID, "y must be 8-byte aligned");
+    for (int i = 0; i < n_layers; ++i)
+        if (misaligned(params[i].conv_weight, 16)) return fail(FD_ERR_INVALID, "layer %d: conv_weight must be 16-byte aligned", i);
     return plan->dtype == FD_BF16 ? train_forward_t<fd_bf16>(plan, params, n_layers, bn_eps, bn_momentum, x_nchw, y, stream)
                                   : train_forward_t<float>(plan, params, n_layers, bn_eps, bn_momentum, x_nchw, y, stream);
 }

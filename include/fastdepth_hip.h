@@ -121,7 +121,19 @@ int fd_plan_create(const fd_layer_desc *layers, int32_t n_layers, int32_t batch,
 void fd_plan_destroy(fd_plan *plan);
 
 /* Bytes of device memory the plan needs (packed weights + activation arena); the caller allocates
- * it (e.g. a torch uint8 tensor) and binds it.  The pointer must be 256-byte aligned. */
+ * it (e.g. a torch uint8 tensor) and binds it.  The pointer must be 256-byte aligned.
+ *
+ * Alignment of the other caller buffers (fd_forward, fd_forward_timed, fd_train_forward, fd_train_backward*); a pointer that
+ * misses its requirement is refused with FD_ERR_INVALID before anything is launched:
+ *   x_nchw                      16 bytes: the stem kernels stage whole input rows with 16-byte loads (width % 32 == 0 keeps every
+ *                               row, plane and frame of an aligned batch aligned, so a frame slice of a contiguous batch qualifies)
+ *   y                           8 bytes: the head kernels write the prediction as pairs of horizontally adjacent pixels
+ *   fd_layer_params.conv_weight 16 bytes in the train entry points, which read the live weights with 16-byte loads
+ *                               (fd_plan_pack_weights reads every parameter element by element: 4 bytes suffice there)
+ *   dy, every fd_layer_grads tensor, bn_weight / bn_bias / bn_mean / bn_var (4 bytes) and bn_num_batches_tracked (8 bytes):
+ *                               their natural alignment only; all accesses are element-wise, and nothing is written beyond a
+ *                               tensor's last element, so gradient tensors may lie back to back in one buffer
+ * Every tensor is dense (contiguous) in the layout named at its entry point. */
 size_t fd_plan_workspace_bytes(const fd_plan *plan);
 int fd_plan_bind_workspace(fd_plan *plan, void *device_ptr, size_t bytes);
 

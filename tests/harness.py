@@ -26,10 +26,81 @@ def get_lib(kind):
     return _libs[kind]
 
 
-class CPlan:
-    """fd_plan + workspace for `model` at x's shape on x's device."""
+def bits_of(t):
+    """A tensor's bytes as a numpy array on the CPU (a copy: it survives the tensor's next use)."""
+    return t.contiguous().view(-1).view(torch.uint8).cpu().numpy().copy()
 
-    def __init__(self, kind, model, x, keep=True, dtype=torch.float32, flags=0):
+
+class Arena:
+    """Caller buffers as views of ONE allocation filled with `pattern` bytes.  items: (key, dtype, shape).  Default layout: every view starts on a 16-byte
+    boundary (its natural alignment as a fresh tensor) `shift` bytes further if asked, with at least `guard` pattern bytes before the first, between two and
+    after the last.  offsets = {key: byte offset}: the views lie exactly there, relative to a 16-byte aligned origin (a flat buffer's layout, nothing between
+    two views but what the offsets leave), with `guard` pattern bytes before the origin and after the last view.  bad_guards() counts the bytes outside
+    the views that no longer hold the pattern."""
+
+    def __init__(self, dev, items, guard=64, pattern=0xA5, offsets=None, shift=None):
+        assert guard % 16 == 0
+        self.pattern, shift = pattern, shift or {}
+        sizes = {k: torch.empty((), dtype=dt).element_size() * int(np.prod(shape, dtype=np.int64)) for k, dt, shape in items}
+        if offsets is None:
+            offsets, pos = {}, 0
+            for k, _, _ in items:
+                offsets[k] = pos + shift.get(k, 0)
+                pos = (offsets[k] + sizes[k] + guard + 15) // 16 * 16
+        end = max(offsets[k] + sizes[k] for k, _, _ in items)
+        self.raw = torch.full((guard + end + guard + 16,), pattern, dtype=torch.uint8, device=dev)
+        org = (-self.raw.data_ptr()) % 16 + guard
+        mask = torch.ones(self.raw.numel(), dtype=torch.bool)
+        self.views, self.span = {}, {}
+        for k, dt, shape in items:
+            o = org + offsets[k]
+            assert not bool((~mask[o:o + sizes[k]]).any()), "overlapping views"
+            mask[o:o + sizes[k]] = False
+            self.span[k] = (o, sizes[k])
+            self.views[k] = self.raw[o:o + sizes[k]].view(dt).view(*shape)
+        self.gmask = mask.to(dev)
+        self.guard_bytes = int(mask.sum())
+
+    def view(self, key):
+        return self.views[key]
+
+    def ptr(self, key):
+        return self.raw.data_ptr() + self.span[key][0]
+
+    def bad_guards(self):
+        return int((self.raw[self.gmask] != self.pattern).sum())
+
+    def first_bad_guard(self):
+        """(key of the nearest view, byte offset relative to that view's end) of the first changed guard byte, or None."""
+        bad = torch.nonzero(self.gmask & (self.raw != self.pattern))
+        if not bad.numel():
+            return None
+        b = int(bad[0])
+        k = min(self.span, key=lambda q: min(abs(b - self.span[q][0]), abs(b - sum(self.span[q]))))
+        return k, b - sum(self.span[k])
+
+
+def _workspace(dev, nbytes, fill, guard, zero_default):
+    """(allocation, 256-byte aligned base address): today's allocation when nothing is asked for; otherwise the whole allocation is set to `fill` bytes and
+    holds `guard` of them before the base and behind base + nbytes."""
+    if fill is None and not guard:
+        ws = (torch.zeros if zero_default else torch.empty)(nbytes + 256, dtype=torch.uint8, device=dev)
+        return ws, (ws.data_ptr() + 255) // 256 * 256
+    fill = (0 if zero_default else 0xA5) if fill is None else fill
+    ws = torch.full((guard + 256 + nbytes + guard,), fill, dtype=torch.uint8, device=dev)
+    return ws, (ws.data_ptr() + guard + 255) // 256 * 256
+
+
+def _bad_guards(ws, base, nbytes, fill):
+    o = base - ws.data_ptr()
+    return int((ws[:o] != fill).sum()) + int((ws[o + nbytes:] != fill).sum())
+
+
+class CPlan:
+    """fd_plan + workspace for `model` at x's shape on x's device.  fill / guard: see _workspace; bundle: the plan is not built from the module but imported
+    from that exported host buffer (fd_plan_import -> bind -> fd_plan_import_weights); pack = False: no weights are packed (the plan's geometry only: info(), raw())."""
+
+    def __init__(self, kind, model, x, keep=True, dtype=torch.float32, flags=0, fill=None, guard=0, bundle=None, pack=True, param_shift=0):
         self.lib = L = get_lib(kind)
         self.kind, self.model, self.dev = kind, model, x.device
         self.dtype = dtype
@@ -39,30 +110,76 @@ class CPlan:
         descs = (capi.LayerDesc * n)(*[l.desc for l in self.layers])
         self.h = ctypes.c_void_p()
         b, _, hh, ww = x.shape
-        capi.check(L, capi.create_plan(L, False, descs, n, b, hh, ww, fd_dtype, (capi.FD_PLAN_KEEP_ACTIVATIONS if keep else 0) | flags,
-                                       ctypes.byref(self.h)), "fd_plan_create")
-        nbytes = L.fd_plan_workspace_bytes(self.h)
-        self.ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.dev)
-        self.base = (self.ws.data_ptr() + 255) // 256 * 256
+        if bundle is None:
+            capi.check(L, capi.create_plan(L, False, descs, n, b, hh, ww, fd_dtype, (capi.FD_PLAN_KEEP_ACTIVATIONS if keep else 0) | flags,
+                                           ctypes.byref(self.h)), "fd_plan_create")
+        else:
+            capi.check(L, L.fd_plan_import(bundle, len(bundle), b, ctypes.byref(self.h)), "fd_plan_import")
+        self.nbytes = nbytes = L.fd_plan_workspace_bytes(self.h)
+        self.fill = (0xA5 if guard else None) if fill is None else fill
+        self.ws, self.base = _workspace(self.dev, nbytes, fill, guard, False)
         capi.check(L, L.fd_plan_bind_workspace(self.h, self.base, nbytes), "fd_plan_bind_workspace")
         self.stream = torch.cuda.current_stream().cuda_stream if x.is_cuda else None
+        self.io = self.pa = None
+        if bundle is not None:
+            capi.check(L, L.fd_plan_import_weights(self.h, bundle, len(bundle), self.stream), "fd_plan_import_weights")
+        if bundle is not None or not pack:
+            return
         params = (capi.LayerParams * n)()
         self._keepalive = []
-        for q, l in zip(params, self.layers):
-            for name, t in (("conv_weight", l.conv.weight), ("bn_weight", l.bn.weight), ("bn_bias", l.bn.bias),
-                            ("bn_mean", l.bn.running_mean), ("bn_var", l.bn.running_var)):
+        src = [(("conv_weight", l.conv.weight), ("bn_weight", l.bn.weight), ("bn_bias", l.bn.bias), ("bn_mean", l.bn.running_mean), ("bn_var", l.bn.running_var)) for l in self.layers]
+        if param_shift:      # the parameters as views of one Arena (self.pa), every one `param_shift` bytes past a 16-byte boundary
+            self.pa = Arena(self.dev, [((i, name), torch.float32, tuple(t.shape)) for i in range(n) for name, t in src[i]],
+                            shift={(i, name): param_shift for i in range(n) for name, _ in src[i]})
+        for i, q in enumerate(params):
+            for name, t in src[i]:
                 t = t.detach().to(self.dev, torch.float32).contiguous()
+                if param_shift:
+                    self.pa.view((i, name)).copy_(t)
+                    t = self.pa.view((i, name))
                 self._keepalive.append(t)
                 setattr(q, name, t.data_ptr())
         capi.check(L, L.fd_plan_pack_weights(self.h, params, n, self.layers[0].bn.eps, self.stream), "fd_plan_pack_weights")
 
-    def forward(self, x):
+    def forward(self, x, guarded=False, shift=None):
+        """guarded: x and y are views of one Arena (self.io) with guard bytes around and between them; shift = {"x" / "y": bytes past the 16-byte boundary}."""
         x = x.contiguous()
-        y = torch.full((x.shape[0], 1, x.shape[2], x.shape[3]), float("nan"), dtype=torch.float32, device=self.dev)
+        yshape = (x.shape[0], 1, x.shape[2], x.shape[3])
+        if guarded:
+            self.io = Arena(self.dev, [("x", torch.float32, tuple(x.shape)), ("y", torch.float32, yshape)], shift=shift)
+            self.io.view("x").copy_(x)
+            x, y = self.io.view("x"), self.io.view("y")
+            y.fill_(float("nan"))
+        else:
+            y = torch.full(yshape, float("nan"), dtype=torch.float32, device=self.dev)
         capi.check(self.lib, self.lib.fd_forward(self.h, x.data_ptr(), y.data_ptr(), self.stream), "fd_forward")
         if x.is_cuda:
             torch.cuda.synchronize()
         return y
+
+    def bad_guards(self):
+        """guard bytes around the workspace (and of the last guarded forward's caller buffers) that changed"""
+        assert self.fill is not None, "bad_guards() needs a plan built with fill or guard"
+        return _bad_guards(self.ws, self.base, self.nbytes, self.fill) + sum(a.bad_guards() for a in (self.io, self.pa) if a is not None)
+
+    def export(self):
+        n = self.lib.fd_plan_export_bytes(self.h)
+        buf = (ctypes.c_ubyte * n)()
+        capi.check(self.lib, self.lib.fd_plan_export(self.h, buf, n, self.stream), "fd_plan_export")
+        return buf
+
+    def raw(self, i):
+        """(bytes of layer i's stored tensor, bytes of the alignment padding behind it up to the next 256-byte boundary of the address space, dims),
+        or None where the plan stores no such tensor (fused away / the network output)."""
+        ptr = ctypes.c_void_p()
+        d = [ctypes.c_int32() for _ in range(4)]
+        if self.lib.fd_layer_output(self.h, i, ctypes.byref(ptr), *[ctypes.byref(v) for v in d]) != 0:
+            return None
+        n, h, w, c = [v.value for v in d]
+        nb = n * h * w * c * (4 if self.dtype == torch.float32 else 2)
+        off = ptr.value - self.ws.data_ptr()
+        pad = -(ptr.value + nb) % 256
+        return bits_of(self.ws[off:off + nb]), bits_of(self.ws[off + nb:off + nb + pad]), (n, h, w, c)
 
     def tap(self, i):
         ptr = ctypes.c_void_p()
@@ -132,10 +249,25 @@ def compare_with_oracle(kind, model, x, device, dtype=torch.float32, flags=0):
     return rel_err(y, y_ref), errs, info
 
 
-class CTrainPlan:
-    """fd_train_plan + workspace; parameters are private fp32 copies on the plan's device (running stats get updated in place)."""
+def flat_grad_offsets(layers):
+    """{(layer, kind): byte offset} of the product's flat gradient buffer (fastdepth_hip/train.py: TrainCore.flat_grad -- layer n-1 first, every tensor on a
+    16-byte boundary, up to 3 padding elements behind a tensor)."""
+    offs, off = {}, 0
+    for i in reversed(range(len(layers))):
+        l = layers[i]
+        for kind, p in (("conv_weight", l.conv.weight), ("bn_weight", l.bn.weight), ("bn_bias", l.bn.bias)):
+            offs[(i, kind)] = 4 * off
+            off += (p.numel() + 3) // 4 * 4
+    return offs
 
-    def __init__(self, kind, model, x, keep=False, dtype=torch.float32, flags=0):
+
+class CTrainPlan:
+    """fd_train_plan + workspace; parameters are private fp32 copies on the plan's device (running stats get updated in place).
+    fill / guard: see _workspace (default: the zero-filled workspace of every earlier test).  layout = "guarded": parameters, running statistics and
+    num_batches_tracked are views of one Arena (self.pa), x / y (self.io), dy (self.dio) and the gradients (self.ga) of others, guard bytes everywhere
+    between; layout = "flat": the same, but the gradient views lie at the offsets of the product's flat gradient buffer with nothing between them."""
+
+    def __init__(self, kind, model, x, keep=False, dtype=torch.float32, flags=0, fill=None, guard=0, layout=None, shift=None):
         self.lib = L = get_lib(kind)
         self.dtype = dtype
         self.dev = x.device
@@ -145,26 +277,54 @@ class CTrainPlan:
         self.h = ctypes.c_void_p()
         b, _, hh, ww = x.shape
         capi.check(L, capi.create_plan(L, True, descs, n, b, hh, ww, capi.DTYPE_OF[dtype], (capi.FD_PLAN_KEEP_ACTIVATIONS if keep else 0) | flags, ctypes.byref(self.h)), "fd_train_plan_create")
-        nbytes = L.fd_train_plan_workspace_bytes(self.h)
-        self.ws = torch.zeros(nbytes + 256, dtype=torch.uint8, device=self.dev)
-        base = (self.ws.data_ptr() + 255) // 256 * 256
-        capi.check(L, L.fd_train_plan_bind_workspace(self.h, base, nbytes), "fd_train_plan_bind_workspace")
+        self.nbytes = nbytes = L.fd_train_plan_workspace_bytes(self.h)
+        self.fill = 0 if fill is None else fill
+        self.ws, self.base = _workspace(self.dev, nbytes, fill, guard, True)
+        capi.check(L, L.fd_train_plan_bind_workspace(self.h, self.base, nbytes), "fd_train_plan_bind_workspace")
         self.stream = torch.cuda.current_stream().cuda_stream if x.is_cuda else None
         self.params = (capi.LayerParams * n)()
         self.tensors = []          # per layer: dict name -> tensor
-        for q, l in zip(self.params, self.layers):
+        self.layout, self.shift = layout, shift or {}
+        self.pa = self.ga = self.io = self.dio = self.nbt = None
+        names = ("conv_weight", "bn_weight", "bn_bias", "bn_mean", "bn_var")
+        src = [dict(zip(names, (l.conv.weight, l.bn.weight, l.bn.bias, l.bn.running_mean, l.bn.running_var))) for l in self.layers]
+        if layout:
+            self.pa = Arena(self.dev, [((i, k), torch.float32, tuple(src[i][k].shape)) for i in range(n) for k in names] + [("nbt", torch.int64, (n,))], shift=self.shift)
+            self.nbt = self.pa.view("nbt")
+            self.nbt.zero_()
+        for i, (q, l) in enumerate(zip(self.params, self.layers)):
             d = {}
-            for name, t in (("conv_weight", l.conv.weight), ("bn_weight", l.bn.weight), ("bn_bias", l.bn.bias),
-                            ("bn_mean", l.bn.running_mean), ("bn_var", l.bn.running_var)):
-                d[name] = t.detach().to(self.dev, torch.float32).contiguous().clone()
+            for name in names:
+                t = src[i][name].detach().to(self.dev, torch.float32).contiguous()
+                if layout:
+                    d[name] = self.pa.view((i, name))
+                    d[name].copy_(t)
+                else:
+                    d[name] = t.clone()
                 setattr(q, name, d[name].data_ptr())
+            if layout:
+                q.bn_num_batches_tracked = self.nbt[i:i + 1].data_ptr()
             self.tensors.append(d)
         self.eps, self.momentum = self.layers[0].bn.eps, self.layers[0].bn.momentum
 
+    def bad_guards(self):
+        """guard bytes around the workspace and around / between all caller buffers that changed"""
+        return _bad_guards(self.ws, self.base, self.nbytes, self.fill) + sum(a.bad_guards() for a in (self.pa, self.ga, self.io, self.dio) if a is not None)
+
+    def guard_bytes(self):
+        return self.ws.numel() - self.nbytes + sum(a.guard_bytes for a in (self.pa, self.ga, self.io, self.dio) if a is not None)
+
     def forward(self, x):
         x = x.contiguous()
+        yshape = (x.shape[0], 1, x.shape[2], x.shape[3])
+        if self.layout:
+            self.io = Arena(self.dev, [("x", torch.float32, tuple(x.shape)), ("y", torch.float32, yshape)], shift=self.shift)
+            self.io.view("x").copy_(x)
+            x, y = self.io.view("x"), self.io.view("y")
+            y.fill_(float("nan"))
+        else:
+            y = torch.full(yshape, float("nan"), dtype=torch.float32, device=self.dev)
         self._x = x                 # fd_train_backward re-reads the network input (stem weight gradient): keep it alive
-        y = torch.full((x.shape[0], 1, x.shape[2], x.shape[3]), float("nan"), dtype=torch.float32, device=self.dev)
         capi.check(self.lib, self.lib.fd_train_forward(self.h, self.params, self.n, self.eps, self.momentum, x.data_ptr(), y.data_ptr(), self.stream), "fd_train_forward")
         if x.is_cuda:
             torch.cuda.synchronize()
@@ -173,16 +333,38 @@ class CTrainPlan:
     def backward(self, dy):
         self.grads = (capi.LayerGrads * self.n)()
         self.grad_tensors = []
-        for g, d in zip(self.grads, self.tensors):
-            gd = {k: torch.full_like(d[k], float("nan")) for k in ("conv_weight", "bn_weight", "bn_bias")}
+        kinds = ("conv_weight", "bn_weight", "bn_bias")
+        if self.layout:
+            items = [((i, k), torch.float32, tuple(self.tensors[i][k].shape)) for i in range(self.n) for k in kinds]
+            self.ga = Arena(self.dev, items, offsets=flat_grad_offsets(self.layers) if self.layout == "flat" else None, shift=self.shift)
+        for i, (g, d) in enumerate(zip(self.grads, self.tensors)):
+            gd = {k: (self.ga.view((i, k)) if self.layout else torch.empty_like(d[k])) for k in kinds}
             for k, t in gd.items():
+                t.fill_(float("nan"))
                 setattr(g, k, t.data_ptr())
             self.grad_tensors.append(gd)
         dy = dy.to(self.dev).contiguous()
+        if self.layout:
+            self.dio = Arena(self.dev, [("dy", torch.float32, tuple(dy.shape))], shift=self.shift)
+            self.dio.view("dy").copy_(dy)
+            dy = self.dio.view("dy")
         capi.check(self.lib, self.lib.fd_train_backward(self.h, self.params, self.grads, self.n, dy.data_ptr(), self.stream), "fd_train_backward")
         if dy.is_cuda:
             torch.cuda.synchronize()
         return self.grad_tensors
+
+    def raw(self, i, which):
+        """(bytes of the tensor fd_train_layer_tensor exposes, bytes of the alignment padding behind it up to the next 256-byte boundary), or None"""
+        ptr = ctypes.c_void_p()
+        d = [ctypes.c_int32() for _ in range(4)]
+        if self.lib.fd_train_layer_tensor(self.h, i, which, ctypes.byref(ptr), *[ctypes.byref(v) for v in d]) != 0 or not ptr.value:
+            return None
+        n, h, w, c = [v.value for v in d]
+        dt = torch.float32 if (which == 2 or i == self.n - 1) else self.dtype
+        nb = n * h * w * c * dt.itemsize
+        off = ptr.value - self.ws.data_ptr()
+        pad = -(ptr.value + nb) % 256
+        return bits_of(self.ws[off:off + nb]), bits_of(self.ws[off + nb:off + nb + pad])
 
     def tensor(self, i, which=0):
         ptr = ctypes.c_void_p()
