@@ -116,18 +116,22 @@ int launch_pw(const fd_plan *plan, const Layer &L, const float *A, const float *
             fz.store_pw = (plan->flags & FD_PLAN_KEEP_ACTIVATIONS) ? 1 : 0;
             fdw = D.d.ksize;
         }
-#define FD_PW16_LAUNCH(TMV, FD_) \
-        do { (void)hipFuncSetAttribute((const void *)fd_pw_gemm16_f32<TMV, FD_G16_STAGES, ACT, 0, FD_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds); \
-             FD_LAUNCH((fd_pw_gemm16_f32<TMV, FD_G16_STAGES, ACT, 0, FD_>), L.grid, dim3(512), L.lds, s, A, wp, bias, out, (int)M, N, K, L.w_pitch, L.pw16_stride, L.m_tiles, L.n_tiles, fz, fd_g16_train{}); } while (0)
+        constexpr int BR = FD_G16_STAGES == 4 ? 1 : 0;         // (the register form of the weight fragments exists for the 4-stage ring: g16_breg_pick)
+#define FD_PW16_LAUNCH(TMV, FD_, BREGV) \
+        do { (void)hipFuncSetAttribute((const void *)fd_pw_gemm16_f32<TMV, FD_G16_STAGES, ACT, 0, FD_, 0, BREGV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds); \
+             FD_LAUNCH((fd_pw_gemm16_f32<TMV, FD_G16_STAGES, ACT, 0, FD_, 0, BREGV>), L.grid, dim3(512), L.lds, s, A, wp, bias, out, (int)M, N, K, L.w_pitch, L.pw16_stride, L.m_tiles, L.n_tiles, fz, fd_g16_train{}); } while (0)
+#define FD_PW16_FDW(TMV, BREGV) \
+        do { if (fdw == 3) FD_PW16_LAUNCH(TMV, 3, BREGV); else if (fdw == 5) FD_PW16_LAUNCH(TMV, 5, BREGV); else FD_PW16_LAUNCH(TMV, 0, BREGV); } while (0)
 #define FD_PW16_CASE(TMV) \
-    case TMV: if (fdw == 3) FD_PW16_LAUNCH(TMV, 3); else if (fdw == 5) FD_PW16_LAUNCH(TMV, 5); else FD_PW16_LAUNCH(TMV, 0); break;
+    case TMV: if (L.pw16_breg) FD_PW16_FDW(TMV, BR); else FD_PW16_FDW(TMV, 0); break;
         switch (L.pw16_tm) {
-            FD_PW16_CASE(13)
+        case 13: FD_PW16_FDW(13, 0); break;                   // (TM = 13 has no register form: g16_breg_pick)
             FD_PW16_CASE(7)
             FD_PW16_CASE(4)
         default: return fail(FD_ERR_INVALID, "no gemm16 instance for TM=%d", L.pw16_tm);
         }
 #undef FD_PW16_CASE
+#undef FD_PW16_FDW
 #undef FD_PW16_LAUNCH
         return check_launch("fd_pw_gemm16_f32");
     }

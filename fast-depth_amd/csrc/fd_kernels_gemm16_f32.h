@@ -47,7 +47,8 @@ struct fd_dwfuse {
 };
 
 #ifdef FD_GEMM16_PROBE
-__device__ long long fd_gemm16_probe[4 * 4096];          // measurement aid (tools/microbench/gemm16.hip): shader-clock and 100 MHz timestamps per workgroup
+__device__ long long fd_gemm16_probe[8 * 4096];          // measurement aid (tools/microbench/gemm16.hip): per workgroup, shader clock at [0] entry, [1] finished image (before the
+                                                         // global stores), [4] first K tile in LDS (K loop starts), [5] K loop done, [6] wave 0 done; [2], [3]: 100 MHz counter at [0], [1]
 #endif
 
 // Train-mode forward (TRAIN = the PRODUCER's activation, FD_ACT_RELU_ / FD_ACT_RELU6_; 0 = inference): the same kernel with
@@ -70,17 +71,49 @@ struct fd_g16_train {
 // ABL (measurement aid, 0 in the product): 1 = no LDS-DMA in the steady state (stages keep the first tiles), 2 = also no fragment reads,
 // 3 = also no per-tile barrier, 4 = full K loop but no global stores -- wrong results, used by tools/microbench/gemm16.hip to price each
 // ingredient of the kernel.
-template <int TM, int STAGES, int ACT, int ABL = 0, int FDW = 0, int TRAIN = 0>
+//
+// BREG = 1: the weight fragments never pass through LDS.  A weight row fragment has exactly one reader -- wave (kh, wn) multiplies columns
+// n0 + wn*16 + (lane & 15) by k-chunk kh*4 + (lane >> 4) of every K tile, 16 bytes per lane -- so the L2 -> LDS-DMA -> LDS -> ds_read_b128 trip
+// buys no reuse; it costs the leaders ceil((BM+64)/32) instead of ceil(BM/32) DMA pieces per K tile (9 / 6 / 4 against 7 / 4 / 2 for TM = 13 / 7 / 4),
+// a quarter to a half of every stage, and one fragment read per wave and K tile.  Here the ring holds the A rows only and every wave
+// loads ITS fragment of K tile t straight into registers (b_load: one plain 16-byte global load per lane: the very bytes fb[] held,
+// so operands, MFMA order and results are those of the LDS form, bit for bit), STAGES tiles ahead, in a register ring of STAGES slots
+// (slot t % STAGES; the K loop is unrolled STAGES times so that every slot is a fixed register quad).
+// vmcnt accounting with BREG -- vector-memory operations complete in order and the loads share the counter with the DMA pieces.  A wave issues
+//   prologue:  B(0) DMA(0) B(1) DMA(1) ... B(S-1) DMA(S-1)                    (DMA(k) = the RG pieces of K tile k: leaders only; S = STAGES)
+//   step t:    DMA(t+S) spread through the MFMAs, B(t+S) after the LAST MFMA  (it overwrites the slot the step's MFMAs read)
+// in this order: FD_SCHED_FENCE keeps the scheduler from moving a load across its neighbours.
+// * The leader's counted wait, top of step t (before the rendezvous behind the prologue: "t = -1"): tile t+1 must have landed.  Behind DMA(t+1) the wave
+//   has issued the tiles t+2 ... t+S-1 in full, RG + 1 operations each, plus -- once t+1 >= S -- the B(t+1) that ends the step of DMA(t+1): vmcnt((S-2)*(RG+1)) asks for DMA(t+1) and, at most, for that one load, which the next step needs anyway.  The count holds while all of those
+//   tiles exist, t+S-1 < T; beyond that the run-time path waits for vmcnt(0).  In the last four steps behind steady-state steps (T - 4 + j, nothing left
+//   to issue) the same argument leaves (2 - j) full steps behind DMA(t+1): vmcnt((2-j)*(RG+1)).
+// * The waits for the weight fragments themselves are the COMPILER's (plain loads), and what it emits differs by role (gfx950 ISA of this kernel):
+//   - followers: a counted wait.  Their queue holds weight fragments only; on the branch-free path the wait before the MFMAs of step t is vmcnt(3),
+//     the three younger fragments stay in flight.
+//   - leaders: NOT a counted wait.  The compiler treats global_load_lds as an access to both memories, and while one is outstanding any wait it needs
+//     on a vector-memory result becomes  s_waitcnt vmcnt(0) lgkmcnt(0).  On the branch-free path it places exactly one such wait per four K tiles:
+//     before the first MFMA of the step on slot 0, at the top of every iteration of the four-step loop.  That wait drains the leader's whole queue --
+//     the DMA pieces of tiles t+1 ... t+3 and the fragments of slots 1 ... 3 -- so in that step the leader's own vmcnt((S-2)*(RG+1)) behind it is moot,
+//     and the three other steps of the iteration need no compiler wait at all (their fragments arrived with the drain); there the hand count alone
+//     decides.  The register form therefore keeps the DMA ring S-1 tiles ahead in three steps of four, not in all; it was measured with this wait
+//     in place and still gains at TM = 7 / 4.  Removing the drain needs loads the compiler cannot see.
+//   - run-time path (K shorter than 2 S tiles; the last T % 4 + 4 steps of a K that is no multiple of four tiles): conditional operations do not count
+//     for the compiler, its waits are vmcnt(0) in both roles: correct, and off the product's shapes (K = 256 / 512 / 1024).
+// Inference only: in train mode (the producer's BatchNorm applied to the A fragments in the MFMA stream) the register form measured slower
+//  and is not built.
+template <int TM, int STAGES, int ACT, int ABL = 0, int FDW = 0, int TRAIN = 0, int BREG = 0>
 __global__ void __launch_bounds__(512)
 fd_pw_gemm16_f32(const float *__restrict__ A, const float *__restrict__ Wt, const float *__restrict__ bias,
                  float *__restrict__ out, int M, int N, int K, int K32, int m_stride, int m_tiles, int n_tiles, const fd_dwfuse fz, const fd_g16_train tr)
 {
     static_assert(TRAIN == 0 || (FDW == 0 && ACT == 0), "train mode: raw output, no fused consumer");
-    constexpr int BM = TM * 16, BN = 64, BK = 32, ROWS = BM + BN;
+    static_assert(BREG == 0 || (STAGES == 4 && (ABL == 0 || ABL == 4) && TRAIN == 0), "the register ring of the weight fragments is written for 4 stages, inference only (and has no K-loop ablations)");
+    constexpr int BM = TM * 16, BN = 64, BK = 32, ROWS = BM + (BREG ? 0 : BN);
     constexpr int STAGE = ROWS * BK;                        // floats per stage
     constexpr int NG = ROWS / 8;                            // LDS-DMA row groups (8 rows = 1 KiB) per stage
     constexpr int RG = (NG + 3) / 4;                        // per leader wave (a leader without an own group in the last round repeats its first)
     constexpr int OP = BN + 4;                              // row pitch (floats) of the output tile image in LDS
+    // (the zero-bordered image of a fused consumer can exceed the A-only ring of BREG: the host asks for the larger of ring and image -- g16_ring_bytes, plan_fuse_epilogues)
     static_assert(STAGES * STAGE >= BM * OP + (TRAIN != 0 ? 8 * 2 * 64 : 0), "the output tile image (+ the statistics scratch) must fit the ring");
     FD_DYN_SMEM(smem_raw);
     float *smem = reinterpret_cast<float *>(smem_raw);
@@ -93,7 +126,7 @@ fd_pw_gemm16_f32(const float *__restrict__ A, const float *__restrict__ Wt, cons
     const int n0 = nt * BN;
     const bool leader = kh == 0;
 #ifdef FD_GEMM16_PROBE
-    long long pc0 = 0, pw0 = 0;
+    long long pc0 = 0, pw0 = 0, pc1 = 0;
     if (tid == 0) { pc0 = clock64(); pw0 = wall_clock64(); }
 #endif
 
@@ -116,7 +149,7 @@ fd_pw_gemm16_f32(const float *__restrict__ A, const float *__restrict__ Wt, cons
     auto piece = [&](int t, int i) {
         int g = wn_u + 4 * i;
         if (g >= NG) g = wn_u;
-        const bool is_a = g < BM / 8;                         // a row group is all A rows or all weight rows (BM % 8 == 0)
+        const bool is_a = BREG != 0 || g < BM / 8;            // a row group is all A rows or all weight rows (BM % 8 == 0)
         const char *base = reinterpret_cast<const char *>(is_a ? A : Wt) + (size_t)t * (BK * 4);
         const char *p = base + src_off[i];
         if (ragged_k && is_a && t == K32 / BK - 1) {         // ragged K, last tile: chunks beyond K read this row's first chunk instead (any
@@ -141,7 +174,11 @@ fd_pw_gemm16_f32(const float *__restrict__ A, const float *__restrict__ Wt, cons
     const int b_off = rowb * BK + ((chunk ^ ((rowb >> 1) & 7)) << 2);
 
     const int T = K32 / BK;
-    fd_f32x4 fa[2][TM], fb[2];
+    // BREG: this lane's 16 bytes of weight K tile t (zero beyond K: the rows are padded to K32)
+    const float *b_src = Wt + (long)(col < N ? col : N - 1) * K32 + chunk * 4;
+    auto b_load = [&](int t) { return fd_ld4(b_src + (size_t)t * BK); };
+
+    fd_f32x4 fa[2][TM], fb[BREG ? STAGES : 2];
     float *tab = smem + STAGES * STAGE;                      // TRAIN: [2][K32] scale / shift of the producer (0 beyond K)
     fd_f32x4 sv[2], tv[2];                                   // ... of this lane's four k of the K tile in fragment buffer 0 / 1
     // (requested now, stored to LDS after the prologue's LDS-DMA has been issued: the table's round trip runs under the first tiles' -- the loads are OLDER
@@ -158,14 +195,25 @@ fd_pw_gemm16_f32(const float *__restrict__ A, const float *__restrict__ Wt, cons
     }
     // One K tile: 4*TM MFMAs on the fragments in buffer B with the loads spread through the MFMA stream: the leader's DMA pieces of
     // tile t+STAGES first, then (both roles) the fragment reads of tile t+1.  The uniform branches also pin the instruction order.
-    auto step = [&](auto buf, auto role, int t) {
-        constexpr int B = decltype(buf)::value;
+    // BREG: `buf` is the slot of the weight-fragment ring, t % STAGES (the A fragments alternate between buffers buf & 1), and `mode` says what the
+    // step knows at compile time -- 0: nothing (run-time conditions, any t), 1: steady state (t + STAGES < T: everything is issued),
+    // 2 + j: step j of the LAST four K tiles behind steady-state steps (nothing left to issue).
+    auto step = [&](auto buf, auto role, int t, auto mode) __attribute__((always_inline)) {
+        constexpr int FB = decltype(buf)::value, B = BREG ? (FB & 1) : FB, MODE = decltype(mode)::value;
         constexpr bool LEAD = decltype(role)::value != 0;
-        constexpr int NDMA = LEAD ? RG : 0, NL = NDMA + TM + 1, SP = (4 * TM) / NL;
+        constexpr int NDMA = LEAD ? RG : 0, NL = NDMA + TM + (BREG ? 0 : 1), SP = (4 * TM) / NL;
         static_assert(SP >= 1, "not enough MFMA slots for the loads");
-        const bool do_frags = ABL != 2 && ABL != 3 && t + 1 < T, do_dma = ABL != 1 && ABL != 2 && ABL != 3 && t + STAGES < T;
-        if (ABL != 3 && t + 1 < T) {
-            if (LEAD) { if ((ABL == 0 || ABL == 4) && t + STAGES - 1 < T) fd_wait_vmcnt<(STAGES - 2) * RG>(); else fd_wait_vmcnt<0>(); }   // tile t+1 has landed
+        static_assert(MODE == 0 || BREG != 0, "the LDS form decides everything at run time");
+        const bool do_frags = MODE == 1 || (MODE >= 2 && MODE < 5) || (MODE == 0 && ABL != 2 && ABL != 3 && t + 1 < T);
+        const bool do_dma = MODE == 1 || (MODE == 0 && ABL != 1 && ABL != 2 && ABL != 3 && t + STAGES < T);
+        if (BREG && MODE == 1) {
+            if (LEAD) fd_wait_vmcnt<(STAGES - 2) * (RG + 1)>();
+            fd_block_barrier_lds();
+        } else if (BREG && MODE >= 2) {
+            if (MODE < 5) { if (LEAD) fd_wait_vmcnt<(MODE < 5 ? 4 - MODE : 0) * (RG + 1)>(); fd_block_barrier_lds(); }
+        } else if (ABL != 3 && t + 1 < T) {
+            if (LEAD && BREG) { if (t + STAGES - 1 < T) fd_wait_vmcnt<(STAGES - 2) * (RG + 1)>(); else fd_wait_vmcnt<0>(); }
+            else if (LEAD) { if ((ABL == 0 || ABL == 4) && t + STAGES - 1 < T) fd_wait_vmcnt<(STAGES - 2) * RG>(); else fd_wait_vmcnt<0>(); }   // tile t+1 has landed
             fd_block_barrier_lds();                          // ... for every leader, and every wave has finished reading tile t's fragments
         }
         const float *nxa = smem + ((t + 1) % STAGES) * STAGE + a_off0, *nxb = smem + ((t + 1) % STAGES) * STAGE + b_off;
@@ -179,63 +227,149 @@ fd_pw_gemm16_f32(const float *__restrict__ A, const float *__restrict__ Wt, cons
                 for (int j = 0; j < FD_G16_TRAIN_AHEAD && j < TM; ++j) fa[B][j] = fd_act4<TRAIN>(fa[B][j] * sv[B] + tv[B]);
             }
             if (TRAIN != 0 && q == 0 && i + FD_G16_TRAIN_AHEAD < TM) fa[B][i + FD_G16_TRAIN_AHEAD] = fd_act4<TRAIN>(fa[B][i + FD_G16_TRAIN_AHEAD] * sv[B] + tv[B]);
-            acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[B][i][q], fb[B][q], acc[i], 0, 0, 0);
+            acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[B][i][q], fb[FB][q], acc[i], 0, 0, 0);
             if ((idx + 1) % SP == 0) {
                 const int l = (idx + 1) / SP - 1;            // load slot
                 if (l < NDMA) {
                     if (do_dma) piece(t + STAGES, l);        // stage t % STAGES is free again: tile t+STAGES goes there
                 } else if (l < NDMA + TM) {
                     if (do_frags) fa[1 - B][l - NDMA] = fd_ld4(nxa + (l - NDMA) * 16 * BK);
-                } else if (l == NDMA + TM) {
+                } else if (!BREG && l == NDMA + TM) {
                     if (do_frags) fb[1 - B] = fd_ld4(nxb);
                 }
             }
         }
-    };
-
-    if (leader) {
-#pragma unroll
-        for (int s = 0; s < STAGES; ++s)
-            if (s < T) {
-#pragma unroll
-                for (int i = 0; i < RG; ++i) piece(s, i);
-            }
-        if (T >= STAGES) fd_wait_vmcnt<(STAGES - 1) * RG>(); else fd_wait_vmcnt<0>();
-    }
-    if (TRAIN != 0) {
-        if (tr.fin.rows) {
-            if (!leader) fd_stat_table_all<256>(tr.fin, K, K32, tid - 256, blockIdx.x == 0, [&](int k, float a, float b) { tab[k] = a; tab[K32 + k] = b; });
-        } else {
-#pragma unroll
-            for (int j = 0; j < TABQ; ++j) { const int k = tid + 512 * j; if (k < K32) { tab[k] = tsc[j]; tab[K32 + k] = tsh[j]; } }
+        if (BREG) {                                          // behind the last MFMA that reads the slot, and at a fixed place in the wave's vector-memory queue
+            FD_SCHED_FENCE();
+            if (do_dma) fb[FB] = b_load(t + STAGES);
+            FD_SCHED_FENCE();
         }
-        fd_block_barrier_lds();
-    } else {
-        fd_block_barrier();
-    }
-    {
+    };
+    // the rendezvous behind the prologue and the first tile's fragments
+    auto first_frags = [&]() __attribute__((always_inline)) {
+        if (TRAIN != 0) {
+            if (tr.fin.rows) {
+                if (!leader) fd_stat_table_all<256>(tr.fin, K, K32, tid - 256, blockIdx.x == 0, [&](int k, float a, float b) { tab[k] = a; tab[K32 + k] = b; });
+            } else {
+#pragma unroll
+                for (int j = 0; j < TABQ; ++j) { const int k = tid + 512 * j; if (k < K32) { tab[k] = tsc[j]; tab[K32 + k] = tsh[j]; } }
+            }
+            fd_block_barrier_lds();
+        } else {
+            fd_block_barrier();
+        }
 #pragma unroll
         for (int i = 0; i < TM; ++i) fa[0][i] = fd_ld4(smem + a_off0 + i * 16 * BK);
-        fb[0] = fd_ld4(smem + b_off);
+        if (!BREG) fb[0] = fd_ld4(smem + b_off);
         if (TRAIN != 0) { sv[0] = fd_ld4(tab + chunk * 4); tv[0] = fd_ld4(tab + K32 + chunk * 4); }
-    }
-    if (leader) {
-#ifndef FD_EMU
-        __builtin_amdgcn_s_setprio(1);
+#ifdef FD_GEMM16_PROBE
+        if (tid == 0) pc1 = clock64();
 #endif
-        for (int t = 0; t < T; t += 2) {
-            step(fd_int<0>{}, fd_int<1>{}, t);
-            if (t + 1 < T) step(fd_int<1>{}, fd_int<1>{}, t + 1);
-        }
+    };
+
+    if constexpr (BREG != 0) {
+        // Each role runs its own copy of prologue, rendezvous and K loop, and K >= 2 * STAGES tiles take a branch-free path: with a conditional vector-memory
+        // operation between a fragment's load and its use the compiler waits for vmcnt(0) at EVERY step; without one the followers get counted waits and
+        // the leaders one drain per four K tiles (see the accounting above the kernel); shorter reductions and the steps of a K that is no multiple of four
+        // tiles run on run-time conditions -- correct by the same compiler-inserted waits, merely stricter than they need to be.
+        auto run = [&](auto role) __attribute__((always_inline)) {
+            constexpr bool LEAD = decltype(role)::value != 0;
+            auto rest = [&](int t0) __attribute__((always_inline)) {
+                for (int t = t0; t < T; t += 4) {
+                    step(fd_int<0>{}, role, t, fd_int<0>{});
+                    if (t + 1 < T) step(fd_int<1>{}, role, t + 1, fd_int<0>{});
+                    if (t + 2 < T) step(fd_int<2>{}, role, t + 2, fd_int<0>{});
+                    if (t + 3 < T) step(fd_int<3>{}, role, t + 3, fd_int<0>{});
+                }
+            };
+            if (T >= 2 * STAGES) {
+#pragma unroll
+                for (int s = 0; s < STAGES; ++s) {
+                    fb[s] = b_load(s);
+                    FD_SCHED_FENCE();                        // (the counted waits rely on this order)
+                    if (LEAD) {
+#pragma unroll
+                        for (int i = 0; i < RG; ++i) piece(s, i);
+                    }
+                    FD_SCHED_FENCE();
+                }
+                if (LEAD) fd_wait_vmcnt<(STAGES - 1) * (RG + 1)>();
+                first_frags();
 #ifndef FD_EMU
-        __builtin_amdgcn_s_setprio(0);
+                if (LEAD) __builtin_amdgcn_s_setprio(1);
 #endif
+                int t = 0;
+                for (; t + 2 * STAGES <= T; t += 4) {
+                    step(fd_int<0>{}, role, t, fd_int<1>{});
+                    step(fd_int<1>{}, role, t + 1, fd_int<1>{});
+                    step(fd_int<2>{}, role, t + 2, fd_int<1>{});
+                    step(fd_int<3>{}, role, t + 3, fd_int<1>{});
+                }
+                if (T - t == 4) {
+                    step(fd_int<0>{}, role, t, fd_int<2>{});
+                    step(fd_int<1>{}, role, t + 1, fd_int<3>{});
+                    step(fd_int<2>{}, role, t + 2, fd_int<4>{});
+                    step(fd_int<3>{}, role, t + 3, fd_int<5>{});
+                } else {
+                    rest(t);
+                }
+            } else {
+#pragma unroll
+                for (int s = 0; s < STAGES; ++s)
+                    if (s < T) {
+                        fb[s] = b_load(s);
+                        FD_SCHED_FENCE();
+                        if (LEAD) {
+#pragma unroll
+                            for (int i = 0; i < RG; ++i) piece(s, i);
+                        }
+                        FD_SCHED_FENCE();
+                    }
+                if (LEAD) { if (T >= STAGES) fd_wait_vmcnt<(STAGES - 1) * (RG + 1)>(); else fd_wait_vmcnt<0>(); }
+                first_frags();
+#ifndef FD_EMU
+                if (LEAD) __builtin_amdgcn_s_setprio(1);
+#endif
+                rest(0);
+            }
+#ifndef FD_EMU
+            if (LEAD) __builtin_amdgcn_s_setprio(0);
+#endif
+        };
+        if (leader) run(fd_int<1>{}); else run(fd_int<0>{});
     } else {
-        for (int t = 0; t < T; t += 2) {
-            step(fd_int<0>{}, fd_int<0>{}, t);
-            if (t + 1 < T) step(fd_int<1>{}, fd_int<0>{}, t + 1);
+        if (leader) {
+#pragma unroll
+            for (int s = 0; s < STAGES; ++s)
+                if (s < T) {
+#pragma unroll
+                    for (int i = 0; i < RG; ++i) piece(s, i);
+                }
+            if (T >= STAGES) fd_wait_vmcnt<(STAGES - 1) * RG>(); else fd_wait_vmcnt<0>();
+        }
+        first_frags();
+        if (leader) {
+#ifndef FD_EMU
+            __builtin_amdgcn_s_setprio(1);
+#endif
+            for (int t = 0; t < T; t += 2) {
+                step(fd_int<0>{}, fd_int<1>{}, t, fd_int<0>{});
+                if (t + 1 < T) step(fd_int<1>{}, fd_int<1>{}, t + 1, fd_int<0>{});
+            }
+#ifndef FD_EMU
+            __builtin_amdgcn_s_setprio(0);
+#endif
+        } else {
+            for (int t = 0; t < T; t += 2) {
+                step(fd_int<0>{}, fd_int<0>{}, t, fd_int<0>{});
+                if (t + 1 < T) step(fd_int<1>{}, fd_int<0>{}, t + 1, fd_int<0>{});
+            }
         }
     }
+#ifdef FD_GEMM16_PROBE
+    long long pc2 = 0;
+    if (tid == 0) pc2 = clock64();                           // end of the K loop (wave 0: a leader)
+#endif
 
     // ---- epilogue: the two k-halves meet in the [row][col] image of the output tile in LDS.  Every wave deposits the partial sums of
     // the row tiles its partner finishes (leader: [0, H), follower: [H, TM)); the owner adds its own, applies the activation in
@@ -290,7 +424,7 @@ fd_pw_gemm16_f32(const float *__restrict__ A, const float *__restrict__ Wt, cons
     }
     __syncthreads();
 #ifdef FD_GEMM16_PROBE
-    if (tid == 0) { fd_gemm16_probe[4 * blockIdx.x] = pc0; fd_gemm16_probe[4 * blockIdx.x + 1] = clock64(); fd_gemm16_probe[4 * blockIdx.x + 2] = pw0; fd_gemm16_probe[4 * blockIdx.x + 3] = wall_clock64(); }
+    if (tid == 0) { long long *pr = fd_gemm16_probe + 8 * blockIdx.x; pr[0] = pc0; pr[1] = clock64(); pr[2] = pw0; pr[3] = wall_clock64(); pr[4] = pc1; pr[5] = pc2; }
 #endif
     if (ABL == 4) return;
     const int c4 = (lane & 15) * 4;
@@ -358,4 +492,7 @@ fd_pw_gemm16_f32(const float *__restrict__ A, const float *__restrict__ Wt, cons
             }
         }
     }
+#ifdef FD_GEMM16_PROBE
+    if (tid == 0) fd_gemm16_probe[8 * blockIdx.x + 6] = clock64();
+#endif
 }

@@ -218,7 +218,8 @@ int plan_layers(fd_plan *p, const fd_layer_desc *layers, size_t *woff_out)
                     const Pw16Cfg c16 = choose_pw16(M, d.cout, d.cin, (tune & FD_TUNE_FORCE_GEMM16) != 0);
                     if (c16.tm) {
                         L.pw16_tm = c16.tm; L.pw16_stride = c16.stride;
-                        L.lds = (size_t)(dtype == FD_F32 ? FD_G16_STAGES : 4) * (c16.tm * 16 + 64) * 32 * 4;   // (128-byte rows in both kernels; the 16-bit one runs a 4-stage ring)
+                        L.pw16_breg = dtype == FD_F32 && g16_breg_pick(c16.tm, tune);
+                        L.lds = dtype == FD_F32 ? g16_ring_bytes(c16.tm, L.pw16_breg != 0) : (size_t)4 * (c16.tm * 16 + 64) * 32 * 4;   // (128-byte rows in both kernels; the 16-bit one runs a 4-stage ring)
                         L.m_tiles = ceil_div(M, c16.stride); L.n_tiles = ceil_div(d.cout, 64);
                         L.grid = dim3((unsigned)((L.m_tiles + 7) / 8 * 8 * L.n_tiles));
                     }
@@ -293,10 +294,16 @@ void plan_fuse_epilogues(fd_plan *p)
             if (!tm) continue;
             if (stride % hw || D.d.cin % 4) continue;                 // whole frames per workgroup
             if (D.d.upsample && D.d.stride != 1) continue;
-            {   // the zero-bordered frame image (+ one dump row) must fit the kernel's LDS ring
+            {   // the zero-bordered frame image (+ one dump row) must fit the kernel's LDS ring -- or, where the fp32 kernel keeps its weight fragments in
+                // registers, the launch asks for the image's size instead: without the 64 weight rows the ring can be the smaller of the two (two 7x7 frames
+                // with a 5x5 consumer: 243 image rows = 66 KB, ring 57 KB), and the kernel's epilogue zeroes and reads the whole image
                 const int P = D.d.upsample ? (D.d.ksize / 2 + 1) / 2 : D.d.ksize / 2;
                 const long img_rows = (long)(stride / hw) * (Pw.out_h + 2 * P) * (Pw.out_w + 2 * P) + 1;
-                if ((size_t)img_rows * 68 * 4 > lds) continue;
+                const size_t img = (size_t)img_rows * 68 * 4;
+                if (img > lds) {
+                    if (!Pw.pw16_breg || h16_pick || img > g16_ring_bytes(tm, false)) continue;       // (never more than the LDS form's ring: the same pairs fuse in both forms)
+                    Pw.lds = img;
+                }
             }
             if (h16_pick) {
                 Pw.pw16_tm = tm; Pw.pw16_stride = stride; Pw.lds = lds; Pw.m_tiles = m_tiles; Pw.n_tiles = n_tiles;
@@ -508,8 +515,8 @@ void plan_describe(fd_plan *p)
             snprintf(buf, sizeof buf, "head_pw1 up=%d grid=%u", d.upsample, L.grid.x);
         else
             if (L.pw16_tm)
-                snprintf(buf, sizeof buf, "pw_gemm16<TM=%d: %dx64 tile, stride %d> M=%ld N=%d K=%d tiles=%dx%d (%.2f per CU) lds=%zu", L.pw16_tm, L.pw16_tm * 16, L.pw16_stride,
-                         (long)batch * L.out_h * L.out_w, d.cout, d.cin, L.m_tiles, L.n_tiles, L.m_tiles * L.n_tiles / 256.0, L.lds),
+                snprintf(buf, sizeof buf, "pw_gemm16<TM=%d: %dx64 tile, stride %d> M=%ld N=%d K=%d tiles=%dx%d (%.2f per CU) lds=%zu%s", L.pw16_tm, L.pw16_tm * 16, L.pw16_stride,
+                         (long)batch * L.out_h * L.out_w, d.cout, d.cin, L.m_tiles, L.n_tiles, L.m_tiles * L.n_tiles / 256.0, L.lds, L.pw16_breg ? ", weight fragments in registers" : ""),
                 L.fuse_next_dw >= 0 ? (void)snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " + fused dw k%d of layer %d", p->layers[L.fuse_next_dw].d.ksize, L.fuse_next_dw) : (void)0;
             else
             snprintf(buf, sizeof buf, "pw_gemm<%dx%d> M=%ld N=%d K=%d tiles=%dx%d lds=%zu", L.pw.wgm * L.pw.tm * 32,
@@ -530,7 +537,7 @@ void plan_describe(fd_plan *p)
         else if (d.op == FD_OP_DW) snprintf(buf, sizeof buf, "fd_dwconv<%s, %d, %d, %d, %d, %d>", tn, d.ksize, d.stride, L.mode, d.act, L.dw_n);
         else if (L.head) snprintf(buf, sizeof buf, "fd_head_pw1<%s, %d>", tn, d.act);
         else if (L.pw16_tm && dtype != FD_F32) snprintf(buf, sizeof buf, "fd_pw_gemm16_h16<%s, %d, 4, %d, %d, 1>", tn, L.pw16_tm, d.act, L.fuse_next_dw >= 0 ? p->layers[L.fuse_next_dw].d.ksize : 0);
-        else if (L.pw16_tm) snprintf(buf, sizeof buf, "fd_pw_gemm16_f32<%d, %d, %d, 0, %d, 0>", L.pw16_tm, FD_G16_STAGES, d.act, L.fuse_next_dw >= 0 ? p->layers[L.fuse_next_dw].d.ksize : 0);
+        else if (L.pw16_tm) snprintf(buf, sizeof buf, "fd_pw_gemm16_f32<%d, %d, %d, 0, %d, 0, %d>", L.pw16_tm, FD_G16_STAGES, d.act, L.fuse_next_dw >= 0 ? p->layers[L.fuse_next_dw].d.ksize : 0, L.pw16_breg);
         else if (dtype == FD_F32) snprintf(buf, sizeof buf, "fd_pw_gemm_f32<%d, %d, %d, %d, %d>", L.pw.wgm, L.pw.wgn, L.pw.tm, L.pw.tn, d.act);
         else if (L.fuse_head >= 0) snprintf(buf, sizeof buf, "fd_pw_gemm_head_h16<%s, %d>", tn, d.act);
         else snprintf(buf, sizeof buf, "fd_pw_gemm_h16<%s, %d>", tn, d.act);

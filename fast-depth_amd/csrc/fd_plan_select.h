@@ -84,6 +84,7 @@ struct Layer {
     PwCfg pw{};
     int m_tiles = 0, n_tiles = 0, w_pitch = 0;
     int pw16_tm = 0, pw16_stride = 0;   // > 0: fd_pw_gemm16_f32 (16x16x4 MFMA, one workgroup per CU) with TM row tiles and this M stride per workgroup
+    int pw16_breg = 0;                  // ... with its weight fragments loaded straight into registers (template parameter BREG; g16_breg_pick)
     size_t lds = 0;
     dim3 grid;
     std::string info, sym;
@@ -190,6 +191,19 @@ Pw16Cfg choose_pw16(long M, int N, int K, bool force)
     if (best.score < 0.72 || K < 256) best = Pw16Cfg();
     return best;
 }
+
+// fd_pw_gemm16_f32's two forms (fp32 plans): BREG keeps the 64 weight rows of a K tile out of the LDS ring -- every wave loads its own fragment
+// into registers.  FD_TUNE_G16_B_LDS keeps the LDS form everywhere (A/B runs, tests); the register ring is written for 4 stages.
+// Measured at batch 32 (tools/microbench/gemm16.hip -4, profiles/r07/gemm16_breg_ab.txt; us per launch, LDS form / BREG): TM = 7 conv12.3 25.3 / 24.0,
+// conv13.3 44.9 / 42.6, decode_conv2.1 22.7 / 21.6; TM = 4 decode_conv1.1 34.8 / 32.5.  TM = 13 keeps the LDS form: its 52 accumulators + 104 A-fragment
+// registers leave no room for the four fragment slots (the register form spills: 504 ... 616 bytes of scratch per lane, 45.9 against 41.4 us on conv7.3),
+// and the weights are only 64 of its 272 ring rows.  No instance of it is built.
+bool g16_breg_pick(int tm, uint32_t tune)
+{
+    return FD_G16_STAGES == 4 && tm != 13 && !(tune & FD_TUNE_G16_B_LDS);
+}
+// dynamic LDS of an fp32 launch without a fused consumer: the ring (A rows, + the 64 weight rows in the LDS form); it always holds the output tile image
+size_t g16_ring_bytes(int tm, bool breg) { return (size_t)FD_G16_STAGES * (tm * 16 + (breg ? 0 : 64)) * 32 * 4; }
 
 int pw_lds_bytes(const PwCfg &c) { return FD_F32_STAGES * (c.wgm * c.tm * 32 + c.wgn * c.tn * 32) * 32 * 4; }   // 3-stage ring of 128-byte rows
 

@@ -557,7 +557,9 @@ int fd_train_plan_create(const fd_layer_desc *layers, int32_t n_layers, int32_t 
                         L.pw16_tm = c16.tm; L.pw16_stride = c16.stride;
                         L.m_tiles = ceil_div(M, c16.stride); L.n_tiles = ceil_div(d.cout, 64);
                         L.grid = dim3((unsigned)((L.m_tiles + 7) / 8 * 8 * L.n_tiles));
-                        L.lds = (size_t)FD_G16_STAGES * (c16.tm * 16 + 64) * 32 * 4 + (size_t)2 * d.cin * 4;      // ring + the producer's (scale, shift) table
+                        // (train mode keeps the weight rows in the LDS ring: with the BatchNorm transform of the A fragments in the MFMA stream the register form of
+                        // the inference plan measured slower at batch 32 -- TM = 7 45.1 against 44.1 us, TM = 4 39.3 against 38.0 -- and is not built for TRAIN)
+                        L.lds = g16_ring_bytes(c16.tm, false) + (size_t)2 * d.cin * 4;      // ring + the producer's (scale, shift) table
                         L.nblk = L.m_tiles;
                     }
                 }

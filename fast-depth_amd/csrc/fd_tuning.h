@@ -36,7 +36,9 @@
                                              rows are <= 128 (fd_bn_bwd_finalize_block; default: only the apply pass of the 16-bit pointwise units does) */
 #define FD_TUNE_NO_DW5_ROWS 1048576u       /* 16-bit plans: the 5x5 up2 + skip units keep the LDS-tiled fd_dwconv (default since round 6: the row-walking pixel-pair
                                              kernel fd_dw5_rows, fd_kernels_dw5p.h) -- A/B runs and the tests of the older form */
-#define FD_TUNE_ALL 2097151u
+#define FD_TUNE_G16_B_LDS 2097152u         /* fp32 inference plans: every fd_pw_gemm16_f32 launch stages its weight rows through the LDS ring (the form before round 7; default: the
+                                             row-tile counts picked by g16_breg_pick load their weight fragments straight into registers, BREG) -- A/B runs and tests */
+#define FD_TUNE_ALL 4194303u
 
 #ifdef __cplusplus
 extern "C" {

@@ -1,5 +1,6 @@
 // standalone microbench: fd_pw_gemm16_f32 (16x16x4 MFMA, k-split wave pairs, one workgroup per CU) against the 32x32x2 kernel
-// on the pointwise shapes of the network (not product code).  usage: gemm16 [shape index]
+// on the pointwise shapes of the network (not product code).  usage: gemm16 [shape index | -2: K sweep + ablations | -3: shader clock | -4 [iters]: LDS form vs register form (BREG)
+// of the weight fragments on the batch-32 plan's six launch shapes, with the phase table of the probe stamps]
 #define FD_GEMM16_PROBE 1
 #include "../../fast-depth_amd/csrc/fd_kernels_f32.h"
 #include "../../fast-depth_amd/csrc/fd_kernels_gemm16_f32.h"
@@ -37,6 +38,34 @@ float run_new(const float* A, const float* W, const float* bias, float* out, int
   float ms; CK(hipEventElapsedTime(&ms,e0,e1)); return ms/iters*1e3f;
 }
 
+// the product's launches (batch 32): LDS form (BREG = 0) against the register form of the weight fragments (BREG = 1), with the fused depthwise consumer
+// where the plan has one; prints us per launch and the phase table of the probe stamps (mean over the workgroups of the last launch)
+struct Phase { float us; double pro, kloop, epi, ghz; };
+template <int TM, int FDW, int BREG>
+Phase run_form(const float* A, const float* W, const float* bias, float* out, float* dwout, const float* taps, int M, int N, int K, int stride, int fH, int up, int iters) {
+  constexpr int S = 4;
+  int mt=(M+stride-1)/stride, nt=(N+63)/64; size_t lds = (size_t)S*(TM*16+(BREG?0:64))*32*4;
+  fd_dwfuse fz{};
+  if (FDW) {
+    fz.w = taps; fz.b = bias; fz.out = dwout; fz.H = fH; fz.W = fH; fz.S = 1; fz.up = up; fz.hi = 6.0f; fz.store_pw = 0;
+    const int P = up ? (FDW/2+1)/2 : FDW/2;
+    lds = std::max(lds, ((size_t)(stride/(fH*fH))*(fH+2*P)*(fH+2*P)+1)*68*4);
+  }
+  CK(hipFuncSetAttribute((const void*)fd_pw_gemm16_f32<TM,S,2,0,FDW,0,BREG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  dim3 grid((mt+7)/8*8*nt);
+  for (int i=0;i<3;++i) hipLaunchKernelGGL((fd_pw_gemm16_f32<TM,S,2,0,FDW,0,BREG>), grid, dim3(512), lds, 0, A,W,bias,out,M,N,K,(K+31)/32*32,stride,mt,nt, fz, fd_g16_train{});
+  CK(hipEventRecord(e0,0));
+  for (int i=0;i<iters;++i) hipLaunchKernelGGL((fd_pw_gemm16_f32<TM,S,2,0,FDW,0,BREG>), grid, dim3(512), lds, 0, A,W,bias,out,M,N,K,(K+31)/32*32,stride,mt,nt, fz, fd_g16_train{});
+  CK(hipEventRecord(e1,0)); CK(hipEventSynchronize(e1)); CK(hipGetLastError());
+  float ms; CK(hipEventElapsedTime(&ms,e0,e1));
+  std::vector<long long> pr(8*grid.x); CK(hipMemcpyFromSymbol(pr.data(), HIP_SYMBOL(fd_gemm16_probe), pr.size()*8));
+  Phase ph{ms/iters*1e3f, 0, 0, 0, 0}; double cyc = 0, wall = 0; int n = 0;
+  for (unsigned b = 0; b < grid.x; ++b) { const long long* q = &pr[8*b]; if (!q[6] || (int)((b>>3)/nt*8+(b&7)) >= mt) continue;
+    ph.pro += (double)(q[4]-q[0]); ph.kloop += (double)(q[5]-q[4]); ph.epi += (double)(q[6]-q[5]); cyc += (double)(q[1]-q[0]); wall += (double)(q[3]-q[2]); ++n; }
+  ph.pro /= n; ph.kloop /= n; ph.epi /= n; ph.ghz = cyc/wall*0.1;
+  return ph;
+}
+
 static double maxdiff(const float* a, const float* b, size_t n, std::vector<float>& ha, std::vector<float>& hb) {
   ha.resize(n); hb.resize(n);
   CK(hipMemcpy(ha.data(), a, n*4, hipMemcpyDeviceToHost)); CK(hipMemcpy(hb.data(), b, n*4, hipMemcpyDeviceToHost));
@@ -56,11 +85,39 @@ int main(int argc, char** argv) {
                                       {100352,128,128},{100352,128,64},{100352,64,128},{401408,64,32},{401408,32,64},
                                       {12544,408,256},{12544,376,408},{50176,120,256},{200704,56,120},{3136,200,512}};
   std::vector<float> ha, hb;
+  if (only == -4) {   // A/B of the two forms on the six launch shapes of the batch-32 fp32 plan
+    const int iters = argc > 2 ? atoi(argv[2]) : 50;
+    float *dw1, *dw2, *taps; CK(hipMalloc(&dw1,(size_t)6272*1024*4*4)); CK(hipMalloc(&dw2,(size_t)6272*1024*4*4)); CK(hipMalloc(&taps,25*1024*4));
+    CK(hipMemcpy(taps,h.data(),25*1024*4,hipMemcpyHostToDevice));
+    printf("%-34s %-5s %8s | %9s %9s %9s cycles (GHz) | K loop per K tile\n", "launch", "form", "us", "prologue", "K loop", "epilogue");
+    auto show = [&](const char* name, int K, const Phase& a, const Phase& b, double diff) {
+      const Phase* f[2] = {&a, &b};
+      for (int i = 0; i < 2; ++i)
+        printf("%-34s %-5s %8.2f | %9.0f %9.0f %9.0f (%.3f) | %.0f cycles = %.3f us%s\n", name, i ? "BREG" : "LDS", f[i]->us, f[i]->pro, f[i]->kloop, f[i]->epi, f[i]->ghz,
+               f[i]->kloop/((K+31)/32), f[i]->kloop/((K+31)/32)/f[i]->ghz*1e-3, i ? (diff == 0 ? "  outputs bitwise equal" : "  OUTPUTS DIFFER") : "");
+      fflush(stdout);
+    };
+#define AB(name, TM, FDW, M, N, K, stride, fH, up, nout) do { \
+      CK(hipMemset(out, 0, (size_t)(nout)*4)); CK(hipMemset(out2, 0, (size_t)(nout)*4)); \
+      Phase a = run_form<TM,FDW,0>(A,W,bias,FDW?out2:out,out,taps,M,N,K,stride,fH,up,iters); \
+      Phase b = run_form<TM,FDW,1>(A,W,bias,FDW?out:out2,out2,taps,M,N,K,stride,fH,up,iters); \
+      show(name, K, a, b, maxdiff(out, out2, (size_t)(nout), ha, hb)); } while (0)
+    (void)dw1; (void)dw2;
+    AB("conv6.3  6272x512x256 TM13 +dw3", 13, 3, 6272, 512, 256, 196, 14, 0, (size_t)6272*512);
+    AB("conv7.3  6272x512x512 TM13 +dw3", 13, 3, 6272, 512, 512, 196, 14, 0, (size_t)6272*512);
+    AB("conv12.3 1568x1024x512 TM7 +dw3", 7, 3, 1568, 1024, 512, 98, 7, 0, (size_t)1568*1024);
+    AB("conv13.3 1568x1024x1024 TM7 +dw5", 7, 5, 1568, 1024, 1024, 98, 7, 0, (size_t)1568*1024);
+    AB("dec1.1 1568x512x1024 TM4 +dw5up2", 4, 5, 1568, 512, 1024, 49, 7, 1, (size_t)6272*512);
+    AB("dec2.1 6272x256x512 TM7", 7, 0, 6272, 256, 512, 98, 0, 0, (size_t)6272*256);
+    AB("dec3.1 25088x128x256 TM13", 13, 0, 25088, 128, 256, 196, 0, 0, (size_t)25088*128);
+#undef AB
+    return 0;
+  }
   if (only == -3) {   // effective shader clock inside the kernel: clock64() ticks per 100 MHz wall tick, main loop only (before the stores)
     for (int abl : {0, 1, 3}) {
       float t = abl == 0 ? run_new<13,4,0>(A,W,bias,out2,6272,512,2048,196,10) : abl == 1 ? run_new<13,4,1>(A,W,bias,out2,6272,512,2048,196,10) : run_new<13,4,3>(A,W,bias,out2,6272,512,2048,196,10);
-      std::vector<long long> pr(4*256); CK(hipMemcpyFromSymbol(pr.data(), HIP_SYMBOL(fd_gemm16_probe), pr.size()*8));
-      double cyc = 0, wall = 0; for (int b = 0; b < 256; ++b) { cyc += (double)(pr[4*b+1]-pr[4*b]); wall += (double)(pr[4*b+3]-pr[4*b+2]); }
+      std::vector<long long> pr(8*256); CK(hipMemcpyFromSymbol(pr.data(), HIP_SYMBOL(fd_gemm16_probe), pr.size()*8));
+      double cyc = 0, wall = 0; for (int b = 0; b < 256; ++b) { cyc += (double)(pr[8*b+1]-pr[8*b]); wall += (double)(pr[8*b+3]-pr[8*b+2]); }
       printf("ABL=%d K=2048: %.1f us; per workgroup main loop %.0f shader cycles in %.0f ticks of the constant 100 MHz counter -> %.3f GHz\n", abl, t, cyc/256, wall/256, cyc/wall*0.1);
     }
     return 0;
