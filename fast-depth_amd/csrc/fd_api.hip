@@ -14,6 +14,7 @@
 #include "fd_kernels_dwt.h"
 #include "fd_kernels_dws.h"
 #include "fd_kernels_dwb.h"
+#include "fd_kernels_conv.h"
 #include "../../include/fastdepth_hip.h"
 #include "fd_tuning.h"
 
@@ -100,6 +101,24 @@ int fd_plan_pack_weights(fd_plan *plan, const fd_layer_params *params, int32_t n
         const Layer &L = plan->layers[i];
         const fd_layer_params &q = params[i];
         if (!q.conv_weight || !q.bn_weight || !q.bn_bias || !q.bn_mean || !q.bn_var) return fail(FD_ERR_INVALID, "layer %d: null parameter pointer", i);
+        if (L.conv) {                                        // dense convolution: [cout][tap][cin padded to the K tile] in the plan's storage type + the zero line; bias in fp64
+            const size_t cesz = plan->dtype == FD_F32 ? 4 : 2;
+            const int kk = L.d.ksize * L.d.ksize, cpad = L.cv_ktpt * fd_conv_bk(cesz);
+            const long upto = (long)(L.w_bytes / cesz);      // packed rows, then zeros up to the end of the zero line
+            float *cb = reinterpret_cast<float *>(plan->ws + L.b_off);
+            if (plan->dtype == FD_F16)
+                hipLaunchKernelGGL((fd_conv_pack<fd_half>), dim3(ceil_div(upto, 256)), dim3(256), 0, s, q.conv_weight, q.bn_weight, q.bn_var, bn_eps, reinterpret_cast<fd_half *>(plan->ws + L.w_off), L.d.cout, L.d.cin, kk, cpad, upto);
+            else if (plan->dtype == FD_BF16)
+                hipLaunchKernelGGL((fd_conv_pack<fd_bf16>), dim3(ceil_div(upto, 256)), dim3(256), 0, s, q.conv_weight, q.bn_weight, q.bn_var, bn_eps, reinterpret_cast<fd_bf16 *>(plan->ws + L.w_off), L.d.cout, L.d.cin, kk, cpad, upto);
+            else
+                hipLaunchKernelGGL((fd_conv_pack<float>), dim3(ceil_div(upto, 256)), dim3(256), 0, s, q.conv_weight, q.bn_weight, q.bn_var, bn_eps, reinterpret_cast<float *>(plan->ws + L.w_off), L.d.cout, L.d.cin, kk, cpad, upto);
+            int rcc = check_launch("fd_conv_pack");
+            if (rcc) return rcc;
+            hipLaunchKernelGGL(fd_dwt_fold_bias, dim3(ceil_div(L.d.cout, 256)), dim3(256), 0, s, q.bn_weight, q.bn_bias, q.bn_mean, q.bn_var, bn_eps, cb, L.d.cout);
+            rcc = check_launch("fd_dwt_fold_bias");
+            if (rcc) return rcc;
+            continue;
+        }
         const int inner = (int)(L.w_elems / L.d.cout);
         const int transpose = (L.d.op == FD_OP_PW) ? 0 : 1;          // stem/dw kernels want tap-major [inner][cout]
         const int pitch = transpose ? inner : (L.w_pitch ? L.w_pitch : inner);   // pointwise rows are zero-padded to the GEMM's BK

@@ -100,6 +100,49 @@ int launch_dwb(const Layer &L, const T *in, const float *wp, const float *bias, 
     return check_launch("fd_dwb_rows");
 }
 
+// dense k x k convolution: the implicit GEMM (fd_kernels_conv.h), followed by fd_conv_reduce when K is split.  A timed forward (fd_forward_timed) brackets
+// both launches with the layer's one event pair: begin of the GEMM ... end of the reduction
+template <typename T>
+int launch_conv(const fd_plan *p, const Layer &L, const T *in, T *out, hipStream_t s)
+{
+    fd_conv_geo g{};
+    g.H = L.out_h; g.W = L.out_w; g.up = L.d.upsample ? 1 : 0; g.ks = L.d.ksize; g.cin = L.d.cin; g.cout = L.d.cout;
+    g.ktpt = L.cv_ktpt; g.m_tiles = L.m_tiles; g.n_tiles = L.n_tiles; g.tps = L.cv_tps;
+    g.act = L.d.act == FD_ACT_RELU6 ? FD_ACT_RELU6_ : (L.d.act == FD_ACT_RELU ? FD_ACT_RELU_ : FD_ACT_NONE_);
+    const long Ml = (long)p->B * L.out_h * L.out_w;
+    const int M = (int)Ml;
+    const T *wp = reinterpret_cast<const T *>(p->ws + L.w_off), *zero = reinterpret_cast<const T *>(p->ws + L.zero_off);
+    const float *bias = reinterpret_cast<const float *>(p->ws + L.b_off);
+    float *part = L.cv_splits > 1 ? reinterpret_cast<float *>(p->ws + p->conv_part_off) : nullptr;
+    const bool split = L.cv_splits > 1;
+    hipEvent_t ev0 = fd_hs().ev_start, ev1 = fd_hs().ev_stop;
+    if (split && ev0) fd_hs().ev_stop = nullptr;             // (the reduction carries the end event)
+#define FD_CONV_CASE(a, b, c, d) \
+    case a * 1000 + b * 100 + c * 10 + d: \
+        if (L.lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)fd_conv_gemm<T, a, b, c, d>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds); \
+        FD_LAUNCH((fd_conv_gemm<T, a, b, c, d>), L.grid, dim3(256), L.lds, s, in, wp, zero, bias, out, part, M, g); break;
+    switch (L.cv_wgm * 1000 + L.cv_wgn * 100 + L.cv_tm * 10 + L.cv_tn) {
+        FD_CONV_CASE(2, 2, 2, 2)
+        FD_CONV_CASE(2, 2, 1, 1)
+        FD_CONV_CASE(4, 1, 1, 1)
+    default: fd_hs().ev_stop = ev1; return fail(FD_ERR_INVALID, "no fd_conv_gemm tile %dx%dx%dx%d", L.cv_wgm, L.cv_wgn, L.cv_tm, L.cv_tn);
+    }
+#undef FD_CONV_CASE
+    fd_hs().ev_stop = ev1;
+    int rc = check_launch("fd_conv_gemm");
+    if (rc || !split) return rc;
+    const long total = Ml * L.d.cout;
+    if (ev0) fd_hs().ev_start = nullptr;
+#ifndef FD_EMU
+    if (ev0 && !fd_hs().trace_on)
+        hipExtLaunchKernelGGL((fd_conv_reduce<T>), dim3(ceil_div(total / 4, 256)), dim3(256), 0, s, nullptr, ev1, 0, part, out, total, L.cv_splits, g.act);
+    else
+#endif
+        FD_LAUNCH((fd_conv_reduce<T>), dim3(ceil_div(total / 4, 256)), dim3(256), 0, s, part, out, total, L.cv_splits, g.act);
+    fd_hs().ev_start = ev0;
+    return check_launch("fd_conv_reduce");
+}
+
 template <int ACT>
 int launch_pw(const fd_plan *plan, const Layer &L, const float *A, const float *wp, const float *bias, float *out, long M, hipStream_t s)
 {
@@ -255,6 +298,7 @@ int launch_layer(const fd_plan *p, const Layer &L, const float *x, float *y, hip
     case FD_OP_STEM: return launch_stem<T, ACT>(L, x, wpf, bias, out, p->B, s);
     case FD_OP_DW: return launch_dw<T, ACT>(L, in, skip, wpf, bias, out, s, L.dw5_cl ? reinterpret_cast<const unsigned *>(p->ws + L.wpk_off) : nullptr);
     case FD_OP_DWT: return launch_dwt<T, ACT>(L, in, wpf, bias, out, s);
+    case FD_OP_CONV: return launch_conv<T>(p, L, in, out, s);
     case FD_OP_DWS: return launch_dws<T, ACT>(L, in, wpf, bias, out, s);
     case FD_OP_PWS:
         FD_LAUNCH((fd_head_shuffle<T, ACT>), L.grid, dim3(256), 0, s, in, wpf, bias, y, (long)p->B * L.out_h * L.out_w, L.out_h, L.out_w, L.d.cin);

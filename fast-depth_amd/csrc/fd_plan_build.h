@@ -188,6 +188,39 @@ int plan_layers(fd_plan *p, const fd_layer_desc *layers, size_t *woff_out)
             L.w_bytes = (size_t)d.cin * 4; L.w_elems = (size_t)d.cin;
             L.grid = dim3(ceil_div(L.in_w, FD_HEADB_TILE), ceil_div(L.in_h, FD_HEADB_TILE), batch);
             break;
+        case FD_OP_CONV: {
+            // dense k x k convolution as an implicit GEMM on the matrix cores (fd_kernels_conv.h): M = batch * map, N = cout, K = k^2 * cin tap-major
+            const int q = dtype == FD_F32 ? 4 : 8;
+            if (d.src < 0 || (d.ksize != 3 && d.ksize != 5) || d.stride != 1 || (d.upsample != 0 && d.upsample != 1) || d.skip >= 0 || concat || d.cin % q || d.cout % q)
+                FD_BAD("layer %d: dense convolution (FD_OP_CONV) needs k in {3,5}, stride 1, cin and cout multiples of %d, upsample 0 or 1, no skip / concat", i, q);
+            const long M = (long)batch * L.in_h * L.in_w;
+            if (M >= (1L << 31) || (double)M * d.cout >= 9.0e18) FD_BAD("layer %d: dense convolution (FD_OP_CONV) over %ld output pixels exceeds the kernel's row indexing", i, M);
+            L.conv = true;
+            L.out_h = L.in_h; L.out_w = L.in_w;
+            const int bk = fd_conv_bk(esz);
+            L.cv_ktpt = ceil_div(d.cin, bk);
+            // tile: 128 x 32 for a narrow N (no idle accumulator columns), 128 x 128 where both sides fill it, else 64 x 64
+            if (d.cout <= 32) { L.cv_wgm = 4; L.cv_wgn = 1; L.cv_tm = 1; L.cv_tn = 1; }
+            else if (d.cout >= 128 && M >= 1024) { L.cv_wgm = 2; L.cv_wgn = 2; L.cv_tm = 2; L.cv_tn = 2; }
+            else { L.cv_wgm = 2; L.cv_wgn = 2; L.cv_tm = 1; L.cv_tn = 1; }
+            const int bm = L.cv_wgm * L.cv_tm * 32, bn = L.cv_wgn * L.cv_tn * 32;
+            L.m_tiles = ceil_div(M, bm); L.n_tiles = ceil_div(d.cout, bn);
+            // split K while the output tiles alone leave CUs idle: the K tiles (tap-major) are dealt to `splits` workgroups per tile, reduced in split order
+            const int kt = d.ksize * d.ksize * L.cv_ktpt;
+            const long tiles = (long)L.m_tiles * L.n_tiles;
+            // (at least 8 K tiles per split: the ring's prologue and the partial tile's round trip have to be paid for)
+            int splits = tiles >= 128 ? 1 : (int)std::min<long>(std::min(kt / 8, 32), 256 / tiles);
+            L.cv_tps = ceil_div(kt, std::max(1, splits));
+            L.cv_splits = ceil_div(kt, L.cv_tps);
+            L.lds = (size_t)FD_CONV_STAGES * (bm + bn) * 128;
+            L.grid = dim3((unsigned)((L.m_tiles + 7) / 8 * 8 * L.n_tiles), (unsigned)L.cv_splits);
+            L.w_elems = (size_t)d.ksize * d.ksize * d.cin * d.cout;
+            const size_t packed = (size_t)d.cout * kt * bk * esz;      // [cout][tap][cin padded to the K tile]: does not depend on the batch (deploy bundles)
+            L.zero_off = align_up(packed, 256);                        // (relative to w_off; made absolute below)
+            L.w_bytes = L.zero_off + FD_CONV_ZERO_BYTES;
+            if (L.cv_splits > 1) p->conv_part_bytes = std::max(p->conv_part_bytes, align_up((size_t)L.cv_splits * M * d.cout * 4, 256));
+            break;
+        }
         case FD_OP_PW:
             if (d.src < 0 || d.ksize != 1 || d.stride != 1 || d.cin % 4) FD_BAD("layer %d: pointwise needs k=1 stride=1 cin%%4==0", i);
             L.out_h = L.in_h; L.out_w = L.in_w;
@@ -236,6 +269,7 @@ int plan_layers(fd_plan *p, const fd_layer_desc *layers, size_t *woff_out)
             FD_BAD("layer %d: a %dx%d map with %d channels exceeds the kernels' 32-bit within-image addressing", i, big_h, big_w, std::max(d.cin, d.cout));
         L.w_off = woff; woff += align_up(L.w_bytes, 256);
         if (L.dw5_cl) L.wpk_off += L.w_off;
+        if (L.conv) L.zero_off += L.w_off;
         L.b_off = woff; woff += align_up((size_t)d.cout * 4, 256);
         L.out_bytes = align_up((size_t)batch * L.out_h * L.out_w * d.cout * esz, 256);
         L.pw_packed_t = (d.op == FD_OP_PW && !L.head && dtype != FD_F32);
@@ -446,7 +480,8 @@ void plan_arena(fd_plan *p, size_t woff)
         // kernel's own inputs are still being read (it must not reuse a buffer that becomes free only after this layer)
         if (L.fuse_next_dw >= 0) p->layers[L.fuse_next_dw].out_off = woff + fl.alloc(p->layers[L.fuse_next_dw].out_bytes);
     }
-    p->ws_bytes = woff + fl.top;
+    p->conv_part_off = align_up(woff + fl.top, 256);
+    p->ws_bytes = p->conv_part_bytes ? p->conv_part_off + p->conv_part_bytes : woff + fl.top;
 
     // bookkeeping: algorithmic traffic and descriptions (SURVEY.md 8(d) convention)
 }
@@ -469,14 +504,16 @@ void plan_describe(fd_plan *p)
         const double out_elems = (double)batch * L.out_h * L.out_w * d.cout;
         const double in_esz = d.src < 0 ? 4.0 : (double)esz, out_esz = L.to_output ? 4.0 : (double)esz;   // network input / output stay fp32
         L.alg_bytes = (src_elems + skip_elems) * in_esz + out_elems * out_esz + (double)L.w_elems * (L.pw_packed_t ? esz : 4) + 2.0 * d.cout * 4;
+        if (L.conv) L.alg_bytes = src_elems * in_esz + out_elems * out_esz + (double)L.w_elems * esz + d.cout * 4.0;   // stored input once, output once, the packed weights, the bias
         p->alg_bytes += L.alg_bytes;
         // (transposed depthwise, polyphase: k^2 / 4 multiply-adds per output)
         // (bilinear layers: the interpolation is not counted; the bilinear head forms its dot products on the half-size map)
-        const double taps = d.op == FD_OP_STEM ? 27.0 : ((d.op == FD_OP_DW || d.op == FD_OP_DWS || d.op == FD_OP_DWB) ? (double)d.ksize * d.ksize : (d.op == FD_OP_DWT ? d.ksize * d.ksize / 4.0 : (double)d.cin));
+        const double taps = d.op == FD_OP_STEM ? 27.0 : ((d.op == FD_OP_DW || d.op == FD_OP_DWS || d.op == FD_OP_DWB) ? (double)d.ksize * d.ksize : (d.op == FD_OP_DWT ? d.ksize * d.ksize / 4.0 : (d.op == FD_OP_CONV ? (double)d.ksize * d.ksize * d.cin : (double)d.cin)));
+        // (dense convolution: the reference's count 2 * k^2 * cin * cout per output pixel)
         const double mac_px = L.pwb ? (double)L.in_h * L.in_w : (double)L.out_h * L.out_w;
         L.alg_flops = 2.0 * batch * mac_px * d.cout * taps;
         p->alg_flops += L.alg_flops;
-        char buf[256];
+        char buf[512];
         if (L.skipped)
             snprintf(buf, sizeof buf, "(fused into layer %d)", i + 1);
         else if (L.fused_into >= 0 && L.head)
@@ -489,6 +526,11 @@ void plan_describe(fd_plan *p)
                      L.fuse_head >= 0 ? " + the 32->1 head on the accumulators" : "");
         else if (d.op == FD_OP_STEM)
             snprintf(buf, sizeof buf, "stem3x3s2<mfma 32x32x2, LDS-staged rows, 256 px per workgroup> grid=%ux%u lds=%zu", L.grid.x, L.grid.y, L.lds);
+        else if (d.op == FD_OP_CONV)
+            snprintf(buf, sizeof buf, "conv_igemm<k%d s1%s, implicit GEMM on mfma %s, all k^2 taps (not pre-summed per parity), tile %dx%d BK %d> M=%ld N=%d K=%dx%d tiles=%dx%d split-K %d%s grid=%ux%u lds=%zu",
+                     d.ksize, d.upsample ? " on up2" : "", dtype == FD_F32 ? "32x32x2 f32" : (dtype == FD_F16 ? "32x32x16 f16" : "32x32x16 bf16"), L.cv_wgm * L.cv_tm * 32, L.cv_wgn * L.cv_tn * 32,
+                     fd_conv_bk(esz), (long)batch * L.out_h * L.out_w, d.cout, d.ksize * d.ksize, d.cin, L.m_tiles, L.n_tiles, L.cv_splits,
+                     L.cv_splits > 1 ? " (fp32 partial tiles + fd_conv_reduce in split order)" : "", L.grid.x, L.grid.y, L.lds);
         else if (d.op == FD_OP_DWT)
             snprintf(buf, sizeof buf, "dwt_rows<k%d s2, polyphase: %d taps per 2x2 output quad, 4 channels per work-item> %d input rows per band, grid=%ux%ux%u, no LDS",
                      d.ksize, d.ksize == 5 ? 25 : 9, L.th, L.grid.x, L.grid.y, L.grid.z);
@@ -527,6 +569,7 @@ void plan_describe(fd_plan *p)
         if (L.skipped || L.fused_into >= 0) buf[0] = 0;
         else if (L.dwpw) snprintf(buf, sizeof buf, "fd_dwpw_f32<%d, %d, %d, %d, %d, %d, %d, %d, 0>", p->layers[L.fused_dw].d.ksize, p->layers[L.fused_dw].d.stride, p->layers[L.fused_dw].mode, d.act, L.dp_wm, L.dp_nt, L.dp_nld, L.fuse_head >= 0 ? 1 : 0);
         else if (d.op == FD_OP_STEM) snprintf(buf, sizeof buf, "fd_stem3x3s2<%s, %d, %d>", tn, d.act, L.chunk);
+        else if (d.op == FD_OP_CONV) snprintf(buf, sizeof buf, "fd_conv_gemm<%s, %d, %d, %d, %d>", tn, L.cv_wgm, L.cv_wgn, L.cv_tm, L.cv_tn);
         else if (d.op == FD_OP_DWT) snprintf(buf, sizeof buf, "fd_dwt_rows<%s, %d, %d>", tn, d.ksize, d.act);
         else if (d.op == FD_OP_DWS) snprintf(buf, sizeof buf, "fd_dws_rows<%s, %d, %d>", tn, d.ksize, d.act);
         else if (d.op == FD_OP_PWS) snprintf(buf, sizeof buf, "fd_head_shuffle<%s, %d>", tn, d.act);

@@ -78,6 +78,10 @@ struct Layer {
     bool pws = false;            // pointwise cin -> 4 written through the pixel shuffle as the network output (FD_OP_PWS): fd_head_shuffle
     bool dwb = false;            // depthwise layer on the bilinear x2 of its producer (FD_OP_DWB): fd_dwb_rows, th source rows per band
     bool pwb = false;            // pointwise cin -> 1 evaluated on the half-size map and interpolated into the network output (FD_OP_PWB): fd_head_bilinear
+    bool conv = false;           // dense k x k convolution (FD_OP_CONV): the implicit GEMM fd_conv_gemm (fd_kernels_conv.h)
+    int cv_wgm = 0, cv_wgn = 0, cv_tm = 0, cv_tn = 0;   // ... its waves (WGM x WGN) and 32 x 32 accumulator tiles per wave (TM x TN)
+    int cv_ktpt = 0, cv_splits = 1, cv_tps = 0;         // ... K tiles per tap, split-K factor (> 1: fd_conv_reduce follows), K tiles per split
+    size_t zero_off = 0;         // ... the zero line behind its packed weights (out-of-map taps, ragged channel tiles)
     // stem
     int chunk = 0;
     // pw
@@ -98,6 +102,7 @@ struct fd_plan {
     int B = 0, H = 0, W = 0, dtype = 0;
     uint32_t flags = 0, tune = 0;    // public plan flags (include/fastdepth_hip.h) / private tuning mask (fd_tuning.h)
     size_t ws_bytes = 0, weights_bytes = 0;
+    size_t conv_part_off = 0, conv_part_bytes = 0;   // fp32 partial tiles of the split-K dense convolutions (one region behind the arena, sized for the largest layer)
     unsigned char *ws = nullptr;
     bool packed = false;
     double alg_bytes = 0, alg_flops = 0;

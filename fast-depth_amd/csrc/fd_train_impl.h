@@ -372,6 +372,7 @@ int fd_train_plan_create(const fd_layer_desc *layers, int32_t n_layers, int32_t 
         L.d = layers[i];
         const fd_layer_desc &d = L.d;
         if (d.src >= i || d.skip >= i) FD_BAD("layer %d: src/skip must reference earlier layers", i);
+        if (d.op == FD_OP_CONV) FD_BAD("layer %d: dense convolution units (FD_OP_CONV) run in inference plans only; their train step is not implemented", i);
         if (d.op == FD_OP_DWT) FD_BAD("layer %d: transposed depthwise units (FD_OP_DWT) run in inference plans only; their train step is not implemented", i);
         if (d.op == FD_OP_DWS || d.op == FD_OP_PWS)
             FD_BAD("layer %d: pixel-shuffle units (%s) run in inference plans only; their train step is not implemented", i, d.op == FD_OP_DWS ? "FD_OP_DWS" : "FD_OP_PWS");

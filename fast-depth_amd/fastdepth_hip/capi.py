@@ -17,7 +17,7 @@ class _DtypeMap(dict):
 
 
 DTYPE_OF = _DtypeMap()      # torch dtype -> fd_dtype (torch imported lazily: this module is also used by tests without torch tensors)
-FD_OP_STEM, FD_OP_DW, FD_OP_PW, FD_OP_DWT, FD_OP_DWS, FD_OP_PWS, FD_OP_DWB, FD_OP_PWB = 0, 1, 2, 3, 4, 5, 6, 7
+FD_OP_STEM, FD_OP_DW, FD_OP_PW, FD_OP_DWT, FD_OP_DWS, FD_OP_PWS, FD_OP_DWB, FD_OP_PWB, FD_OP_CONV = 0, 1, 2, 3, 4, 5, 6, 7, 8
 FD_ACT_NONE, FD_ACT_RELU, FD_ACT_RELU6 = 0, 1, 2
 # public plan flags (include/fastdepth_hip.h)
 FD_PLAN_KEEP_ACTIVATIONS = 1

@@ -11,6 +11,8 @@ The ShuffleConv decoder (`decoder.conv1..4`) puts a 2x pixel shuffle before each
 shuffle (FD_OP_DWS) and its last pointwise layer writes the network output through it (FD_OP_PWS).
 The BLConv decoder (`decoder.conv1..6`, class attribute `_fd_upsample = "bilinear"`) puts a bilinear x2 after conv1..conv5: the depthwise layers
 of conv2..conv5 interpolate their producer's output themselves (FD_OP_DWB), and conv6 is evaluated before the last interpolation (FD_OP_PWB).
+The dense NNConv decoder (`MobileNet('nnconv5' / 'nnconv3')`: `decoder.conv1..5` are ONE dense k x k unit each) takes the same walk as its
+depthwise-separable sibling: its units become FD_OP_CONV layers, conv2..conv5 and the head carrying `upsample`.
 """
 import torch.nn as nn
 
@@ -72,8 +74,10 @@ class Layer:
                 raise capi.FastDepthError("%s: conv %r cannot run as op %r" % (name, conv, op))
         elif isinstance(conv, nn.ConvTranspose2d):     # (validated by _units)
             op = capi.FD_OP_DWT
-        elif conv.groups == 1 and k == 3:
+        elif conv.groups == 1 and k == 3 and conv.in_channels == 3 and conv.stride == (2, 2) and src == -1:
             op = capi.FD_OP_STEM
+        elif conv.groups == 1 and k in (3, 5) and conv.stride == (1, 1):
+            op = capi.FD_OP_CONV       # dense k x k unit of the dense NNConv decoder: the implicit GEMM fd_conv_gemm
         elif conv.groups == conv.in_channels == conv.out_channels and k in (3, 5):
             op = capi.FD_OP_DW
         elif conv.groups == 1 and k == 1:

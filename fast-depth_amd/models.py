@@ -25,7 +25,7 @@ import torch.nn as nn
 
 import imagenet.mobilenet as _mobilenet
 
-__all__ = ["MobileNetSkipAdd", "MobileNetSkipConcat", "MobileNet", "NNConv", "BLConv", "DeConv", "ShuffleConv", "choose_decoder", "depthwise", "pointwise", "weights_init", "PRUNED_CHANNELS"]
+__all__ = ["MobileNetSkipAdd", "MobileNetSkipConcat", "MobileNet", "NNConv", "BLConv", "DeConv", "ShuffleConv", "choose_decoder", "conv", "depthwise", "pointwise", "weights_init", "PRUNED_CHANNELS"]
 
 # Channel plan of `mobilenet-nnconv5dw-skipadd-pruned`, reconstructed from the reference's TVM tuning
 # log (tvm_compile/tuning/tx2-gpu.mobilenet-nnconv5dw-skipadd-pruned.trials=2000.stop=600.log:1-38,
@@ -51,6 +51,14 @@ def weights_init(m):
 
 def _bn_relu(channels):
     return [nn.BatchNorm2d(channels), nn.ReLU(inplace=True)]
+
+
+def conv(in_channels, out_channels, kernel_size):
+    """dense k x k conv (stride 1, pad (k-1)/2, no bias) + BN + ReLU; reference models.py:52-59."""
+    padding = (kernel_size - 1) // 2
+    if 2 * padding != kernel_size - 1:
+        raise AssertionError("parameters incorrect. kernel={}, padding={}".format(kernel_size, padding))
+    return nn.Sequential(nn.Conv2d(in_channels, out_channels, kernel_size, stride=1, padding=padding, bias=False), *_bn_relu(out_channels))
 
 
 def depthwise(in_channels, kernel_size):
@@ -115,19 +123,21 @@ class _HipForward(nn.Module):
 
 
 class NNConv(nn.Module):
-    """Nearest-neighbour-upsampling decoder, depthwise-separable form (reference models.py:224-270 with dw=True):
-    conv1..conv5 = Sequential(depthwise(C, k), pointwise(C, C/2)) for C = 1024..64, conv6 = pointwise(32, 1); the reference's
-    forward interleaves a nearest x2 after conv1..conv5.  Parameter container only (the HIP engine executes it as part of
-    `MobileNet`).  The dense variant (dw=False: k x k full convolutions) is outside this package's kernels."""
+    """Nearest-neighbour-upsampling decoder (reference models.py:224-270).  dw=True, the depthwise-separable form:
+    conv1..conv5 = Sequential(depthwise(C, k), pointwise(C, C/2)) for C = 1024..64.  dw=False, the dense form (the MobileNet-NNConv5
+    baseline of the FastDepth paper): conv1..conv5 = conv(C, C/2, k), one full k x k convolution each, k in {3, 5} -- run by the HIP
+    engine as FD_OP_CONV layers on the implicit GEMM fd_conv_gemm, inference only.  conv6 = pointwise(32, 1) in both; the reference's
+    forward interleaves a nearest x2 after conv1..conv5.  Parameter container only (the HIP engine executes it as part of `MobileNet`)."""
 
     def __init__(self, kernel_size, dw):
         super().__init__()
-        if not dw:
-            raise NotImplementedError("fast-depth_amd implements the depthwise-separable decoders ('nnconv5dw', 'nnconv3dw'); "
-                                      "the dense NNConv decoder is not on the accelerated path")
+        if not dw and kernel_size not in (3, 5):
+            raise NotImplementedError("fast-depth_amd runs the dense NNConv decoder with k in {3, 5} ('nnconv5', 'nnconv3'); "
+                                      "a dense %dx%d unit is not on the accelerated path" % (kernel_size, kernel_size))
         width = 1024
         for j in range(1, 6):
-            setattr(self, 'conv{}'.format(j), nn.Sequential(depthwise(width, kernel_size), pointwise(width, width // 2)))
+            unit = nn.Sequential(depthwise(width, kernel_size), pointwise(width, width // 2)) if dw else conv(width, width // 2, kernel_size)
+            setattr(self, 'conv{}'.format(j), unit)
             width //= 2
         self.conv6 = pointwise(width, 1)
 
@@ -189,6 +199,8 @@ def choose_decoder(decoder):
     """Reference models.py:335-360, restricted to the decoders whose layers are on the accelerated path."""
     if decoder in ('nnconv5dw', 'nnconv3dw'):
         model = NNConv(int(decoder[6]), True)
+    elif decoder in ('nnconv5', 'nnconv3'):
+        model = NNConv(int(decoder[6]), False)
     elif decoder in ('deconv5dw', 'deconv3dw'):
         model = DeConv(int(decoder[6]), True)
     elif decoder in ('shuffle5dw', 'shuffle3dw'):
@@ -196,7 +208,7 @@ def choose_decoder(decoder):
     elif decoder in ('blconv5dw', 'blconv3dw'):
         model = BLConv(int(decoder[6]), True)
     else:
-        raise NotImplementedError("decoder {!r}: only 'nnconv5dw' / 'nnconv3dw' / 'deconv5dw' / 'deconv3dw' / 'shuffle5dw' / 'shuffle3dw' / 'blconv5dw' / 'blconv3dw' "
+        raise NotImplementedError("decoder {!r}: only 'nnconv5dw' / 'nnconv3dw' / 'nnconv5' / 'nnconv3' / 'deconv5dw' / 'deconv3dw' / 'shuffle5dw' / 'shuffle3dw' / 'blconv5dw' / 'blconv3dw' "
                                   "are built by fast-depth_amd "
                                   "(SURVEY.md 8(f) row f-3)".format(decoder))
     model.apply(weights_init)
@@ -206,7 +218,8 @@ def choose_decoder(decoder):
 class MobileNet(_HipForward):
     """MobileNet-v1 encoder + decoder WITHOUT skip connections -- `MobileNet(decoder, output_size, in_channels=3,
     pretrained=True)` as in reference models.py:420-460 (runs on the same kernels as
-    MobileNetSkipAdd, with `skip = -1` everywhere).  Attribute tree and state_dict keys follow the reference:
+    MobileNetSkipAdd, with `skip = -1` everywhere; the dense decoders 'nnconv5' / 'nnconv3' on the implicit-GEMM convolution, inference
+    only).  Attribute tree and state_dict keys follow the reference:
     `mobilenet.0 .. mobilenet.13`, `decoder.conv1 .. decoder.conv6` (NNConv, BLConv) or `decoder.convt1 .. decoder.convt5`, `decoder.convf` (DeConv)
     or `decoder.conv1 .. decoder.conv4` (ShuffleConv)."""
 

@@ -1,6 +1,7 @@
 /*
  * fastdepth_hip.h -- C ABI of libfastdepth_hip.so: the MI355X (gfx950) execution engine for the
- * FastDepth MobileNet-NNConv5(dw)+skip-add hot path.
+ * FastDepth MobileNet-NNConv5(dw)+skip-add hot path, its no-skip siblings with the depthwise-separable decoders, and the dense
+ * NNConv decoder (MobileNet('nnconv5' / 'nnconv3'): FD_OP_CONV).
  *
  * Plain pointers and sizes only; no torch / C++ types.  Device pointers are HIP device pointers of
  * the calling process (torch allocations are fine), `stream` is a hipStream_t passed as void*.
@@ -67,11 +68,16 @@ enum fd_op {
                      * UPSAMPLED map; the upsampled tensor is never stored.  cin == cout == C (a multiple of 2), producer channels == C, stride = 1,
                      * upsample = 0, skip = -1, concat = 0; the output map is 2 x the source map.  conv_weight is torch's [C][1][k][k].
                      * Inference plans only, as FD_OP_DWT. */
-    FD_OP_PWB = 7   /* pointwise cin -> 1 + BatchNorm evaluated on src's map, then interpolated (bilinear x2, as FD_OP_DWB), activated and written as the
+    FD_OP_PWB = 7,  /* pointwise cin -> 1 + BatchNorm evaluated on src's map, then interpolated (bilinear x2, as FD_OP_DWB), activated and written as the
                      * fp32 network output: y = act(up(s pw(src) + t)), which equals act(s pw(up(src)) + t) because the affine part commutes with
                      * an interpolation whose weights sum to 1.  Only valid as the LAST layer, on a map of half the network's height and width;
                      * cin % 4 == 0, cin <= 64, cout == 1, ksize = 1, stride = 1, upsample = 0, skip = -1, concat = 0.  Keeps fp32 weights in every
                      * plan.  Inference plans only, as FD_OP_DWT. */
+    FD_OP_CONV = 8  /* DENSE k x k conv (k = 3 or 5, stride 1, padding (k-1)/2), the unit of the dense NNConv decoder (models.py:52-59, 246-251): an implicit
+                     * GEMM on the matrix cores (M = pixels, N = cout, K = k^2 cin; fp32 accumulation from the folded-BN bias).  src >= 0; upsample = 1: the
+                     * input is the nearest x2 of src's output, read from the stored half-size map (the upsampled tensor is never stored); upsample = 0 or 1,
+                     * skip = -1, concat = 0; cin and cout multiples of 4 (16-bit plans: of 8).  conv_weight is torch's [cout][cin][k][k].
+                     * Inference plans only, as FD_OP_DWT. */
 };
 enum fd_act { FD_ACT_NONE = 0, FD_ACT_RELU = 1, FD_ACT_RELU6 = 2 };
 
@@ -91,7 +97,7 @@ typedef struct fd_layer_desc {
     int32_t op;       /* enum fd_op */
     int32_t cin;
     int32_t cout;     /* == cin for FD_OP_DW / FD_OP_DWT / FD_OP_DWS / FD_OP_DWB */
-    int32_t ksize;    /* 3 (stem, encoder dw), 5 (decoder dw), 1 (pw) */
+    int32_t ksize;    /* 3 (stem, encoder dw), 5 (decoder dw), 1 (pw); FD_OP_CONV: 3 or 5 */
     int32_t stride;   /* 1 or 2 (FD_OP_DWT: 2, the factor by which the map GROWS) */
     int32_t act;      /* enum fd_act */
     int32_t src;      /* index of the layer whose output feeds this one; -1 = network input */
