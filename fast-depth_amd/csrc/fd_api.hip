@@ -71,6 +71,7 @@ int fd_plan_create(const fd_layer_desc *layers, int32_t n_layers, int32_t batch,
     plan_fuse_epilogues(p);
     plan_fuse_units(p);
     plan_fuse_head_h16(p);
+    plan_pick_x3(p);
     plan_arena(p, woff);
     plan_describe(p);
     *out_plan = p;
@@ -135,6 +136,13 @@ int fd_plan_pack_weights(fd_plan *plan, const fd_layer_params *params, int32_t n
                                reinterpret_cast<float *>(plan->ws + L.w_off), bptr, L.d.cout, inner, transpose, pitch);
         int rc = check_launch("fd_pack_fold");
         if (rc) return rc;
+        if (L.wx3_off) {                                     // the bf16 planes of the split-bf16 GEMM form, from the folded rows just written
+            const long n = (long)L.d.cout * L.w_pitch;
+            hipLaunchKernelGGL(fd_pack_x3_planes, dim3(ceil_div(n, 256)), dim3(256), 0, s, reinterpret_cast<const float *>(plan->ws + L.w_off),
+                               reinterpret_cast<unsigned short *>(plan->ws + L.wx3_off), n);
+            rc = check_launch("fd_pack_x3_planes");
+            if (rc) return rc;
+        }
         if (L.dwt || L.dws || L.pws || L.dwb || L.pwb) {     // transposed, pixel-shuffle and bilinear layers: the bias folded in fp64 (fd_kernels_dwt.h)
             hipLaunchKernelGGL(fd_dwt_fold_bias, dim3(ceil_div(L.d.cout, 256)), dim3(256), 0, s, q.bn_weight, q.bn_bias, q.bn_mean, q.bn_var, bn_eps, bptr, L.d.cout);
             rc = check_launch("fd_dwt_fold_bias");
@@ -194,12 +202,39 @@ int fd_layer_output(const fd_plan *plan, int32_t layer, const void **device_ptr,
     if (L.to_output) return fail(FD_ERR_STATE, "the last layer writes the caller's output buffer");
     if (L.skipped) return fail(FD_ERR_STATE, "layer %d is fused into its consumer and has no stored output", layer);
     if (!plan->ws) return fail(FD_ERR_STATE, "no workspace bound");
+    // (KEEP_ACTIVATIONS, checked above: out_off is always the layer's tensor in the plan's storage type.  Only in plans that do not keep activations does a
+    // depthwise layer with out_x3 hold its three bf16 planes there instead -- x3_off == out_off -- and those plans hand out no layer tensors)
     if (device_ptr) *device_ptr = plan->ws + L.out_off;
     if (n) *n = plan->B;
     if (h) *h = L.out_h;
     if (w) *w = L.out_w;
     if (c) *c = L.d.cout;
     return FD_OK;
+}
+
+int fd_plan_x3_tensors(const fd_plan *plan, int32_t layer, const void **out, int64_t *dims)
+{
+    if (!plan || !plan->ws || !out || !dims || layer < 0 || layer >= (int)plan->layers.size()) return -1;
+    const Layer &L = plan->layers[layer];
+    for (int i = 0; i < 5; ++i) { out[i] = nullptr; dims[i] = 0; }
+    if (L.out_x3) {
+        out[0] = plan->ws + L.x3_off;
+        if (plan->flags & FD_PLAN_KEEP_ACTIVATIONS) out[1] = plan->ws + L.out_off;
+        dims[0] = (int64_t)plan->B * L.out_h * L.out_w; dims[1] = (L.d.cout + 31) / 32 * 32;
+    }
+    if (L.wx3_off) {
+        out[2] = plan->ws + L.wx3_off; out[3] = plan->ws + L.w_off; out[4] = plan->ws + L.b_off;
+        dims[2] = L.d.cout; dims[3] = L.w_pitch; dims[4] = L.pw16_x3;
+    }
+    return 0;
+}
+
+int fd_plan_run_gemm16_layer(fd_plan *plan, int32_t layer, void *stream)
+{
+    if (!plan || !plan->ws || !plan->packed || !(plan->flags & FD_PLAN_KEEP_ACTIVATIONS) || layer < 0 || layer >= (int)plan->layers.size()) return -1;
+    const Layer &L = plan->layers[layer];
+    if (L.d.op != FD_OP_PW || !L.pw16_tm || L.head || L.dwpw || L.skipped || L.fused_into >= 0 || L.to_output || L.fuse_head >= 0 || L.d.src < 0) return -1;
+    return run_layer(plan, L, nullptr, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int32_t fd_plan_num_kernels(const fd_plan *plan) { return plan ? (int32_t)plan->layers.size() : 0; }   /* = number of layers; fused-away layers report an empty symbol */
@@ -249,6 +284,10 @@ int fd_plan_layer_traffic(const fd_plan *plan, int32_t layer, double *needed_byt
         b += D.alg_bytes - ((plan->flags & FD_PLAN_KEEP_ACTIVATIONS) ? 1.0 : 2.0) * out_b(L);     // (KEEP_ACTIVATIONS plans still store the pointwise output)
     }
     if (L.fuse_head >= 0) { const Layer &H = plan->layers[L.fuse_head]; b += H.alg_bytes - 2.0 * out_b(L); }
+    // the split-bf16 GEMM form moves 6 bytes per element of its weights and of its A operand, which its producer writes as three bf16 planes
+    // (KEEP_ACTIVATIONS plans: next to the fp32 tensor)
+    if (L.pw16_x3) b += 2.0 * ((double)plan->B * L.out_h * L.out_w * L.d.cin + (double)L.w_elems);
+    if (L.fuse_next_dw >= 0 && plan->layers[L.fuse_next_dw].out_x3) b += out_b(plan->layers[L.fuse_next_dw]) * ((plan->flags & FD_PLAN_KEEP_ACTIVATIONS) ? 1.5 : 0.5);
     *needed_bytes = b;
     return FD_OK;
 }

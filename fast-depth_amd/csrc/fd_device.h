@@ -192,6 +192,29 @@ __device__ __forceinline__ unsigned fd_f32x2_to_bf16x2(float a, float b)
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, fd_bf16x2_hw));
 }
 #endif
+// v_mfma_f32_16x16x32_bf16 on raw bf16 bits: lane l holds A[l & 15][8 (l >> 4) + j], B[8 (l >> 4) + j][l & 15], j = 0..7, and D[4 (l >> 4) + r][l & 15] --
+// the accumulator layout of v_mfma_f32_16x16x4_f32 (the split-bf16 form of fd_pw_gemm16_f32: fd_kernels_gemm16_x3.h)
+#ifdef FD_EMU
+inline fd_f32x4 fd_mfma_bf16_16x16x32(fd_u16x8 a, fd_u16x8 b, fd_f32x4 c) { return hipemu_mfma_f32_16x16x32_bf16(a, b, c); }
+#else
+__device__ __forceinline__ fd_f32x4 fd_mfma_bf16_16x16x32(fd_u16x8 a, fd_u16x8 b, fd_f32x4 c)
+{
+    typedef __bf16 fd_bf16x8_mfma __attribute__((ext_vector_type(8)));
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(fd_bf16x8_mfma, a), __builtin_bit_cast(fd_bf16x8_mfma, b), c, 0, 0, 0);
+}
+#endif
+// Exact split of two fp32 values into three bf16 each (low half = a): hi = bf16(v), mid = bf16(v - hi), lo = bf16(v - hi - mid), round to nearest even; both
+// differences are exact in fp32, so hi + mid + lo == v (evaluated as (hi + mid) + lo in fp32) for every finite v whose bf16 rounding is finite.  A value
+// whose hi part is not finite (Inf, NaN, or a finite v within half a bf16 ulp of overflow) becomes (hi, 0, 0).
+__device__ __forceinline__ void fd_split3_bf16x2(float a, float b, unsigned &hi, unsigned &mid, unsigned &lo)
+{
+    hi = fd_f32x2_to_bf16x2(a, b);
+    const bool fa = (hi & 0x7f80u) != 0x7f80u, fb = (hi & 0x7f800000u) != 0x7f800000u;
+    float ra = fa ? a - fd_bf16_to_f32((unsigned short)hi) : 0.0f, rb = fb ? b - fd_bf16_to_f32((unsigned short)(hi >> 16)) : 0.0f;
+    mid = fd_f32x2_to_bf16x2(ra, rb);
+    ra -= fd_bf16_to_f32((unsigned short)mid); rb -= fd_bf16_to_f32((unsigned short)(mid >> 16));
+    lo = fd_f32x2_to_bf16x2(ra, rb);
+}
 // 4 consecutive channels: one 8-byte access
 __device__ __forceinline__ fd_f32x4 fd_ld4(const fd_half *p)
 {

@@ -158,6 +158,28 @@ int launch_pw(const fd_plan *plan, const Layer &L, const float *A, const float *
             fz.hi = D.d.act == FD_ACT_RELU6 ? 6.0f : __builtin_inff();
             fz.store_pw = (plan->flags & FD_PLAN_KEEP_ACTIVATIONS) ? 1 : 0;
             fdw = D.d.ksize;
+            if (D.out_x3) {                                   // its only reader is a split-bf16 GEMM: the three bf16 planes, instead of the fp32 tensor unless the plan keeps every tensor
+                fz.planes = reinterpret_cast<unsigned short *>(plan->ws + D.x3_off);
+                fz.pM = (long)plan->B * D.out_h * D.out_w; fz.pK32 = (D.d.cout + 31) / 32 * 32;
+                if (!(plan->flags & FD_PLAN_KEEP_ACTIVATIONS)) fz.out = nullptr;
+            }
+        }
+        if (L.pw16_x3) {                                      // split-bf16 form: A = the producer's planes, weights = the layer's planes
+            const float *Ap = reinterpret_cast<const float *>(plan->ws + plan->layers[L.d.src].x3_off), *Wp = reinterpret_cast<const float *>(plan->ws + L.wx3_off);
+#define FD_PW16_X3_LAUNCH(TMV, SV, FD_) \
+        do { (void)hipFuncSetAttribute((const void *)fd_pw_gemm16_f32<TMV, SV, ACT, 0, FD_, 0, 0, FD_G16_X3_FORM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds); \
+             FD_LAUNCH((fd_pw_gemm16_f32<TMV, SV, ACT, 0, FD_, 0, 0, FD_G16_X3_FORM>), L.grid, dim3(512), L.lds, s, Ap, Wp, bias, out, (int)M, N, K, L.w_pitch, L.pw16_stride, L.m_tiles, L.n_tiles, fz, fd_g16_train{}); } while (0)
+#define FD_PW16_X3_CASE(TMV, SV) \
+    case TMV: if (fdw == 3) FD_PW16_X3_LAUNCH(TMV, SV, 3); else if (fdw == 5) FD_PW16_X3_LAUNCH(TMV, SV, 5); else FD_PW16_X3_LAUNCH(TMV, SV, 0); break;
+            switch (L.pw16_tm) {
+                FD_PW16_X3_CASE(13, 3)
+                FD_PW16_X3_CASE(7, 4)
+                FD_PW16_X3_CASE(4, 4)
+            default: return fail(FD_ERR_INVALID, "no split-bf16 gemm16 instance for TM=%d", L.pw16_tm);
+            }
+#undef FD_PW16_X3_CASE
+#undef FD_PW16_X3_LAUNCH
+            return check_launch("fd_pw_gemm16_f32");
         }
         constexpr int BR = FD_G16_STAGES == 4 ? 1 : 0;         // (the register form of the weight fragments exists for the 4-stage ring: g16_breg_pick)
 #define FD_PW16_LAUNCH(TMV, FD_, BREGV) \

@@ -34,6 +34,7 @@
 #pragma once
 #include "fd_device.h"
 #include "fd_bn_stats.h"
+#include "fd_kernels_gemm16_x3.h"
 
 // the depthwise layer fused behind a pointwise GEMM (fd_pw_gemm16_f32<..., FDW = its kernel size>)
 struct fd_dwfuse {
@@ -44,7 +45,26 @@ struct fd_dwfuse {
     int S, up;                 // stride (1 | 2); up = 1: the input is the nearest-x2 upsampling of the frame (S == 1)
     float hi;                  // activation: clamp(0, hi), hi = 6 (ReLU6) or +inf (ReLU)
     int store_pw;              // also store the GEMM's own output (plans that keep every layer's activations)
+    // planes != null: the output's only reader is a split-bf16 GEMM (fd_kernels_gemm16_x3.h), so it is ALSO (out != null) or ONLY (out == null) stored as that
+    // GEMM's A operand -- three bf16 planes, K-tile-major [pK32 / 32][3][pM][32], channels [C, pK32) written as zeros (pK32 <= the 64-column blocks cover)
+    unsigned short *planes;
+    long pM;                   // rows of the consumer GEMM = pixels of this layer's whole output
+    int pK32;                  // its K pitch: C rounded up to 32
 };
+
+// 4 consecutive channels c .. c + 3 (c % 4 == 0) of row m into the three planes (fd_dwfuse::planes layout)
+__device__ __forceinline__ void fd_x3_store4(unsigned short *planes, long pM, long m, int c, fd_f32x4 v)
+{
+    typedef unsigned fd_u32x2_ __attribute__((ext_vector_type(2)));
+    unsigned h0, m0, l0, h1, m1, l1;
+    fd_split3_bf16x2(v.x, v.y, h0, m0, l0);
+    fd_split3_bf16x2(v.z, v.w, h1, m1, l1);
+    unsigned short *p = planes + ((long)(c >> 5) * 3 * pM + m) * 32 + (c & 31);
+    const fd_u32x2_ vh = {h0, h1}, vm = {m0, m1}, vl = {l0, l1};
+    *reinterpret_cast<fd_u32x2_ *>(p) = vh;
+    *reinterpret_cast<fd_u32x2_ *>(p + pM * 32) = vm;
+    *reinterpret_cast<fd_u32x2_ *>(p + 2 * pM * 32) = vl;
+}
 
 #ifdef FD_GEMM16_PROBE
 __device__ long long fd_gemm16_probe[8 * 4096];          // measurement aid (tools/microbench/gemm16.hip): per workgroup, shader clock at [0] entry, [1] finished image (before the
@@ -101,7 +121,13 @@ struct fd_g16_train {
 //     for the compiler, its waits are vmcnt(0) in both roles: correct, and off the product's shapes (K = 256 / 512 / 1024).
 // Inference only: in train mode (the producer's BatchNorm applied to the A fragments in the MFMA stream) the register form measured slower
 //  and is not built.
-template <int TM, int STAGES, int ACT, int ABL = 0, int FDW = 0, int TRAIN = 0, int BREG = 0>
+//
+// X3 != 0: the split-bf16 form (fd_kernels_gemm16_x3.h).  A and Wt point to the three bf16 planes of the operands, the K loop runs six
+// v_mfma_f32_16x16x32_bf16 per row tile and K tile, split 1 + 5 between the two waves of a SIMD (the leader takes a_hi * w_hi alone); tile ownership, XCD
+// numbering and the whole epilogue are those of the fp32 forms (the 16x16 accumulator layout is the same).  The one form built is X3 = 13, the number it
+// had among the variants measured in profiles/r08 (1 = on, 4 = K-tile-major A planes, 8 = the 1 + 5 split; the others lost: DESIGN.md Appendix A).
+// Inference only; selected by g16_x3_pick (fd_plan_select.h), measured by tools/microbench/gemm16.hip -5.
+template <int TM, int STAGES, int ACT, int ABL = 0, int FDW = 0, int TRAIN = 0, int BREG = 0, int X3 = 0>
 __global__ void __launch_bounds__(512)
 fd_pw_gemm16_f32(const float *__restrict__ A, const float *__restrict__ Wt, const float *__restrict__ bias,
                  float *__restrict__ out, int M, int N, int K, int K32, int m_stride, int m_tiles, int n_tiles, const fd_dwfuse fz, const fd_g16_train tr)
@@ -109,7 +135,9 @@ fd_pw_gemm16_f32(const float *__restrict__ A, const float *__restrict__ Wt, cons
     static_assert(TRAIN == 0 || (FDW == 0 && ACT == 0), "train mode: raw output, no fused consumer");
     static_assert(BREG == 0 || (STAGES == 4 && (ABL == 0 || ABL == 4) && TRAIN == 0), "the register ring of the weight fragments is written for 4 stages, inference only (and has no K-loop ablations)");
     constexpr int BM = TM * 16, BN = 64, BK = 32, ROWS = BM + (BREG ? 0 : BN);
-    constexpr int STAGE = ROWS * BK;                        // floats per stage
+    static_assert(X3 == 0 || X3 == 13, "one split-bf16 form is built");
+    static_assert(X3 == 0 || (BREG == 0 && TRAIN == 0 && (ABL == 0 || ABL == 4)), "the split-bf16 form is inference only and has no K-loop ablations");
+    constexpr int STAGE = X3 ? fd_g16_x3_geom<TM, STAGES>::STAGE_B / 4 : ROWS * BK;   // floats per stage
     constexpr int NG = ROWS / 8;                            // LDS-DMA row groups (8 rows = 1 KiB) per stage
     constexpr int RG = (NG + 3) / 4;                        // per leader wave (a leader without an own group in the last round repeats its first)
     constexpr int OP = BN + 4;                              // row pitch (floats) of the output tile image in LDS
@@ -267,7 +295,14 @@ fd_pw_gemm16_f32(const float *__restrict__ A, const float *__restrict__ Wt, cons
 #endif
     };
 
-    if constexpr (BREG != 0) {
+    if constexpr (X3 != 0) {
+        long long *stamp = nullptr;                           // (measurement aid: when the K loop starts)
+#ifdef FD_GEMM16_PROBE
+        stamp = &pc1;
+#endif
+        fd_g16_x3_kloop<TM, STAGES>(reinterpret_cast<const unsigned char *>(A), reinterpret_cast<const unsigned char *>(Wt), smem_raw, acc,
+                                                                   m0, n0, M, N, K32, stamp);
+    } else if constexpr (BREG != 0) {
         // Each role runs its own copy of prologue, rendezvous and K loop, and K >= 2 * STAGES tiles take a branch-free path: with a conditional vector-memory
         // operation between a fragment's load and its use the compiler waits for vmcnt(0) at EVERY step; without one the followers get counted waits and
         // the leaders one drain per four K tiles (see the accounting above the kernel); shorter reductions and the steps of a K that is no multiple of four
@@ -453,7 +488,14 @@ fd_pw_gemm16_f32(const float *__restrict__ A, const float *__restrict__ Wt, cons
         constexpr int PD = KD / 2;
         const int cg = tid & 15, pl = tid >> 4;
         const int c = n0 + cg * 4;
-        if (c >= N) return;
+        if (c >= N) {
+            if (fz.planes && c < fz.pK32) {                  // K padding of the split-bf16 consumer: zeros, whatever the workspace held
+                const int HWp = ((fH << us) / fz.S) * ((fW << us) / fz.S);
+                for (int fr = 0; fr < frames; ++fr)
+                    for (int op = pl; op < HWp; op += 32) fd_x3_store4(fz.planes, fz.pM, (m0 / fHW + fr) * HWp + op, c, fd_zero4());
+            }
+            return;
+        }
         fd_f32x4 wv[KD * KD];
 #pragma unroll
         for (int t = 0; t < KD * KD; ++t) wv[t] = fd_ld4(fz.w + (long)t * N + c);
@@ -486,7 +528,8 @@ fd_pw_gemm16_f32(const float *__restrict__ A, const float *__restrict__ Wt, cons
                 fd_f32x4 r4;
                 r4.x = fd_relu_clamp(a4.x, fz.hi); r4.y = fd_relu_clamp(a4.y, fz.hi);
                 r4.z = fd_relu_clamp(a4.z, fz.hi); r4.w = fd_relu_clamp(a4.w, fz.hi);
-                fd_st4(fz.out + ((f0 + fr) * HWo + op) * N + c, r4);
+                if (fz.out) fd_st4(fz.out + ((f0 + fr) * HWo + op) * N + c, r4);
+                if (fz.planes) fd_x3_store4(fz.planes, fz.pM, (f0 + fr) * HWo + op, c, r4);
                 ox += dx; oy += dy;
                 if (ox >= Wo) { ox -= Wo; ++oy; }
             }

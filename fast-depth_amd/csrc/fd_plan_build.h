@@ -237,6 +237,10 @@ int plan_layers(fd_plan *p, const fd_layer_desc *layers, size_t *woff_out)
                 if (dtype != FD_F32 && d.cin % 8) FD_BAD("layer %d: 16-bit pointwise needs cin %% 8 == 0", i);
                 L.w_pitch = dtype == FD_F32 ? (d.cin + 31) / 32 * 32 : (d.cin + 63) / 64 * 64;   // rows zero-padded to a multiple of BK
                 L.w_bytes = (size_t)d.cout * L.w_pitch * esz;
+                if (dtype == FD_F32) {                         // + the three bf16 planes of the split-bf16 GEMM form (relative to w_off; made absolute below)
+                    L.wx3_off = align_up(L.w_bytes, 256);
+                    L.w_bytes = L.wx3_off + (size_t)d.cout * L.w_pitch * 6;
+                }
                 L.pw = dtype == FD_F32 ? choose_pw(M, d.cout) : PwCfg{2, 2, 1, 1};
                 L.lds = pw_lds_bytes(L.pw);
                 // 16-bit kernel: a reduction of one or two K tiles never touches the ring's later stages -- not requested, so that more workgroups
@@ -269,6 +273,7 @@ int plan_layers(fd_plan *p, const fd_layer_desc *layers, size_t *woff_out)
             FD_BAD("layer %d: a %dx%d map with %d channels exceeds the kernels' 32-bit within-image addressing", i, big_h, big_w, std::max(d.cin, d.cout));
         L.w_off = woff; woff += align_up(L.w_bytes, 256);
         if (L.dw5_cl) L.wpk_off += L.w_off;
+        if (L.wx3_off) L.wx3_off += L.w_off;
         if (L.conv) L.zero_off += L.w_off;
         L.b_off = woff; woff += align_up((size_t)d.cout * 4, 256);
         L.out_bytes = align_up((size_t)batch * L.out_h * L.out_w * d.cout * esz, 256);
@@ -445,6 +450,43 @@ void plan_fuse_head_h16(fd_plan *p)
     // activation arena
 }
 
+// pass 4b: fp32 plans -- one-round pointwise GEMMs on the split-bf16 form (fd_kernels_gemm16_x3.h).  A layer takes it where g16_x3_pick says so, its A operand is
+// produced by the depthwise stage of a gemm16 epilogue (the producer that can store the three bf16 planes) and has no other reader (a KEEP_ACTIVATIONS plan
+// stores the fp32 tensor as well, so there any number of readers will do).  The producer then writes the planes INSTEAD of the fp32 tensor: 6 bytes per element.
+void plan_pick_x3(fd_plan *p)
+{
+    if (p->dtype != FD_F32) return;
+    const int n_layers = (int)p->layers.size();
+    const bool keep = (p->flags & FD_PLAN_KEEP_ACTIVATIONS) != 0;
+    std::vector<int> readers(n_layers, 0);
+    for (int i = 0; i < n_layers; ++i) {
+        if (p->layers[i].d.src >= 0) ++readers[p->layers[i].d.src];
+        if (p->layers[i].d.skip >= 0) ++readers[p->layers[i].d.skip];
+    }
+    for (int i = 0; i < n_layers; ++i) {
+        Layer &L = p->layers[i];
+        if (L.d.op != FD_OP_PW || L.head || L.dwpw || !L.pw16_tm || L.d.src < 0) continue;
+        Layer &D = p->layers[L.d.src];
+        if (D.d.op != FD_OP_DW || D.fused_into < 0 || (readers[L.d.src] != 1 && !keep)) continue;
+        const long M = (long)p->B * L.out_h * L.out_w;
+        if (!g16_x3_pick(L.pw16_tm, M, L.d.cout, L.d.cin, p->tune)) continue;
+        if ((double)M * 3 * 64 >= 4294967296.0) continue;     // the kernel's per-lane LDS-DMA source offsets are 32-bit
+        size_t lds = g16_x3_ring_bytes(L.pw16_tm), fixed = 4;
+        if (L.fuse_next_dw >= 0) {                            // the zero-bordered image of ITS fused consumer, and the kernel's static row map
+            const Layer &C = p->layers[L.fuse_next_dw];
+            const int P = C.d.upsample ? (C.d.ksize / 2 + 1) / 2 : C.d.ksize / 2;
+            const long img_rows = (long)(L.pw16_stride / (L.out_h * L.out_w)) * (L.out_h + 2 * P) * (L.out_w + 2 * P) + 1;
+            lds = std::max(lds, (size_t)img_rows * 68 * 4);
+            fixed = (size_t)L.pw16_tm * 16 * 4;
+        }
+        if (lds + fixed > 160 * 1024) continue;
+        L.pw16_x3 = 1; L.pw16_breg = 0; L.lds = lds;
+        D.out_x3 = true;
+        D.x3_bytes = align_up((size_t)M * L.w_pitch * 6, 256);
+        if (!keep) D.out_bytes = D.x3_bytes;
+    }
+}
+
 // pass 5: lifetime-based activation arena behind the packed weights (woff bytes)
 void plan_arena(fd_plan *p, size_t woff)
 {
@@ -478,7 +520,12 @@ void plan_arena(fd_plan *p, size_t woff)
         L.out_off = woff + fl.alloc(L.out_bytes);
         // a depthwise layer evaluated in this layer's epilogue is WRITTEN by this layer's kernel: its buffer must be live now, while this
         // kernel's own inputs are still being read (it must not reuse a buffer that becomes free only after this layer)
-        if (L.fuse_next_dw >= 0) p->layers[L.fuse_next_dw].out_off = woff + fl.alloc(p->layers[L.fuse_next_dw].out_bytes);
+        if (L.fuse_next_dw >= 0) {
+            Layer &D = p->layers[L.fuse_next_dw];
+            D.out_off = woff + fl.alloc(D.out_bytes);
+            // (the planes of a split-bf16 reader: the layer's only buffer, or a second one where the plan keeps every fp32 tensor)
+            if (D.out_x3) D.x3_off = (flags & FD_PLAN_KEEP_ACTIVATIONS) ? woff + fl.alloc(D.x3_bytes) : D.out_off;
+        }
     }
     p->conv_part_off = align_up(woff + fl.top, 256);
     p->ws_bytes = p->conv_part_bytes ? p->conv_part_off + p->conv_part_bytes : woff + fl.top;
@@ -558,7 +605,7 @@ void plan_describe(fd_plan *p)
         else
             if (L.pw16_tm)
                 snprintf(buf, sizeof buf, "pw_gemm16<TM=%d: %dx64 tile, stride %d> M=%ld N=%d K=%d tiles=%dx%d (%.2f per CU) lds=%zu%s", L.pw16_tm, L.pw16_tm * 16, L.pw16_stride,
-                         (long)batch * L.out_h * L.out_w, d.cout, d.cin, L.m_tiles, L.n_tiles, L.m_tiles * L.n_tiles / 256.0, L.lds, L.pw16_breg ? ", weight fragments in registers" : ""),
+                         (long)batch * L.out_h * L.out_w, d.cout, d.cin, L.m_tiles, L.n_tiles, L.m_tiles * L.n_tiles / 256.0, L.lds, L.pw16_breg ? ", weight fragments in registers" : ""),       // (the split-bf16 form is named by the kernel symbol below: template parameter X3)
                 L.fuse_next_dw >= 0 ? (void)snprintf(buf + strlen(buf), sizeof buf - strlen(buf), " + fused dw k%d of layer %d", p->layers[L.fuse_next_dw].d.ksize, L.fuse_next_dw) : (void)0;
             else
             snprintf(buf, sizeof buf, "pw_gemm<%dx%d> M=%ld N=%d K=%d tiles=%dx%d lds=%zu", L.pw.wgm * L.pw.tm * 32,
@@ -580,7 +627,7 @@ void plan_describe(fd_plan *p)
         else if (d.op == FD_OP_DW) snprintf(buf, sizeof buf, "fd_dwconv<%s, %d, %d, %d, %d, %d>", tn, d.ksize, d.stride, L.mode, d.act, L.dw_n);
         else if (L.head) snprintf(buf, sizeof buf, "fd_head_pw1<%s, %d>", tn, d.act);
         else if (L.pw16_tm && dtype != FD_F32) snprintf(buf, sizeof buf, "fd_pw_gemm16_h16<%s, %d, 4, %d, %d, 1>", tn, L.pw16_tm, d.act, L.fuse_next_dw >= 0 ? p->layers[L.fuse_next_dw].d.ksize : 0);
-        else if (L.pw16_tm) snprintf(buf, sizeof buf, "fd_pw_gemm16_f32<%d, %d, %d, 0, %d, 0, %d>", L.pw16_tm, FD_G16_STAGES, d.act, L.fuse_next_dw >= 0 ? p->layers[L.fuse_next_dw].d.ksize : 0, L.pw16_breg);
+        else if (L.pw16_tm) snprintf(buf, sizeof buf, "fd_pw_gemm16_f32<%d, %d, %d, 0, %d, 0, %d, %d>", L.pw16_tm, L.pw16_x3 ? g16_x3_stages(L.pw16_tm) : FD_G16_STAGES, d.act, L.fuse_next_dw >= 0 ? p->layers[L.fuse_next_dw].d.ksize : 0, L.pw16_breg, L.pw16_x3 ? FD_G16_X3_FORM : 0);
         else if (dtype == FD_F32) snprintf(buf, sizeof buf, "fd_pw_gemm_f32<%d, %d, %d, %d, %d>", L.pw.wgm, L.pw.wgn, L.pw.tm, L.pw.tn, d.act);
         else if (L.fuse_head >= 0) snprintf(buf, sizeof buf, "fd_pw_gemm_head_h16<%s, %d>", tn, d.act);
         else snprintf(buf, sizeof buf, "fd_pw_gemm_h16<%s, %d>", tn, d.act);

@@ -89,6 +89,10 @@ struct Layer {
     int m_tiles = 0, n_tiles = 0, w_pitch = 0;
     int pw16_tm = 0, pw16_stride = 0;   // > 0: fd_pw_gemm16_f32 (16x16x4 MFMA, one workgroup per CU) with TM row tiles and this M stride per workgroup
     int pw16_breg = 0;                  // ... with its weight fragments loaded straight into registers (template parameter BREG; g16_breg_pick)
+    int pw16_x3 = 0;                    // ... in the split-bf16 form (template parameter X3; plan_pick_x3): A = the producer's three bf16 planes, weights = wx3_off
+    size_t wx3_off = 0;                 // fp32 pointwise layers: the three bf16 planes [3][N][K32] of the folded weights, behind the fp32 rows (every such layer has them: the packed weights do not depend on the batch size or on the tuning mask)
+    bool out_x3 = false;                // depthwise layer: its output is stored as the three bf16 planes its only reader, a split-bf16 GEMM, takes as A
+    size_t x3_off = 0, x3_bytes = 0;    // ... where (KEEP_ACTIVATIONS plans: next to the fp32 tensor; otherwise the planes ARE the layer's buffer, x3_off == out_off)
     size_t lds = 0;
     dim3 grid;
     std::string info, sym;
@@ -206,6 +210,22 @@ Pw16Cfg choose_pw16(long M, int N, int K, bool force)
 bool g16_breg_pick(int tm, uint32_t tune)
 {
     return FD_G16_STAGES == 4 && tm != 13 && !(tune & FD_TUNE_G16_B_LDS);
+}
+// The split-bf16 form (fd_kernels_gemm16_x3.h).  Its ring holds the weight planes too (3 (BM + 64) rows of 64 bytes per stage), so TM = 13 runs three stages
+// (156 672 bytes) and TM = 7 / 4 four.  Selection: a launch shape (TM, M, N, K) enters g16_x3_pick only where tools/layer_times.py --batch 32 showed the launch more than
+// 1 us shorter than the fp32 form's in every alternating pass (profiles/r08); FD_TUNE_FORCE_G16_X3 takes every eligible layer, FD_TUNE_NO_G16_X3 none.
+#define FD_G16_X3_FORM 13    // the kernel's X3 value in plans: on (1) + K-tile-major A planes (4) + the leader takes a_hi * w_hi alone (8); the leaders issue the LDS-DMA
+int g16_x3_stages(int tm) { return tm == 13 ? 3 : 4; }
+size_t g16_x3_ring_bytes(int tm) { return (size_t)g16_x3_stages(tm) * 3 * (tm * 16 + 64) * 64; }
+bool g16_x3_pick(int tm, long m, int n, int k, uint32_t tune)
+{
+    if (tune & FD_TUNE_NO_G16_X3) return false;
+    if (tune & FD_TUNE_FORCE_G16_X3) return true;
+    // the measured launch shape of conv7.3 ... conv11.3 at batch 32 (36.8 -> 29.6 us each); other batch sizes keep the fp32 forms until their shapes have been
+    // measured too.  The TM = 7 / 4 launches of that plan (conv12.3, conv13.3, decode_conv1.1, decode_conv2.1) were measured 3.5 - 9.5 us shorter as well
+    // (profiles/r08) but stay on the register form of the fp32 kernel: the committed form table of the default plans (tests/batch_sweep.py) records
+    // `weight fragments in registers` for them, and moving them means regenerating that table -- a change of its own.
+    return tm == 13 && m == 6272 && n == 512 && k == 512;
 }
 // dynamic LDS of an fp32 launch without a fused consumer: the ring (A rows, + the 64 weight rows in the LDS form); it always holds the output tile image
 size_t g16_ring_bytes(int tm, bool breg) { return (size_t)FD_G16_STAGES * (tm * 16 + (breg ? 0 : 64)) * 32 * 4; }

@@ -38,13 +38,26 @@
                                              kernel fd_dw5_rows, fd_kernels_dw5p.h) -- A/B runs and the tests of the older form */
 #define FD_TUNE_G16_B_LDS 2097152u         /* fp32 inference plans: every fd_pw_gemm16_f32 launch stages its weight rows through the LDS ring (the form before round 7; default: the
                                              row-tile counts picked by g16_breg_pick load their weight fragments straight into registers, BREG) -- A/B runs and tests */
-#define FD_TUNE_ALL 4194303u
+#define FD_TUNE_FORCE_G16_X3 4194304u      /* fp32 inference plans: every eligible fd_pw_gemm16_f32 layer (its A operand written by a producer that can store the three bf16 planes) runs the
+                                             split-bf16 form X3 (fd_kernels_gemm16_x3.h), whatever its shape (default: the measured launch shapes of g16_x3_pick) -- tests and A/B runs */
+#define FD_TUNE_NO_G16_X3 8388608u         /* fp32 inference plans: no layer runs the split-bf16 form (the plan before round 8) -- A/B runs and tests */
+#define FD_TUNE_ALL 16777215u
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 /* the mask applies to the next plan this thread creates (then resets to 0); unknown bits are rejected by that creation */
 void fd_tuning_next(uint32_t mask);
+/* Test hook of the split-bf16 GEMM form (fd_kernels_gemm16_x3.h; valid once a workspace is bound).  out[0..5], null where the layer has none:
+ * [0] the three bf16 planes a depthwise layer stores for its split-bf16 reader, K-tile-major [k32 / 32][3][m][32]; [1] the fp32 tensor it also stores
+ * (KEEP_ACTIVATIONS plans); [2] a pointwise layer's weight planes [3][n][wk32], [3] its folded fp32 weight rows [n][wk32], [4] its folded bias [n].
+ * dims[0..4] = m, k32, n, wk32, 1 if the pointwise layer runs the split-bf16 form.  Returns 0, or -1 for bad arguments. */
+struct fd_plan;
+int fd_plan_x3_tensors(const struct fd_plan *plan, int32_t layer, const void **out, int64_t *dims);
+/* Test hook: launches the fd_pw_gemm16_f32 kernel of pointwise layer `layer` alone, on whatever its operands in the workspace hold now (a test
+ * writes the A rows it wants -- non-finite values no producer of a plan lets through -- and reads the layer's stored output; KEEP_ACTIVATIONS plans
+ * only).  Returns FD_OK, or -1 where the layer is no such launch. */
+int fd_plan_run_gemm16_layer(struct fd_plan *plan, int32_t layer, void *stream);
 /* Test hook of the layer-local train parity (tests/harness.py: the fp64 single-unit reference rounds exactly where the kernels round): which
  * kernels of depthwise unit `layer` keep their LDS patches in the 16-bit storage type in the forms the plan chose for it (valid right after creation) --
  * bit 0: the forward kernel rounds its (activated, upsampled, skip-added) conv input; bit 1: the backward kernels round dz and the

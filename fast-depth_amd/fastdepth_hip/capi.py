@@ -51,6 +51,8 @@ FD_TUNE_NO_CONSUMER_FINALIZE = 262144 << _TUNE_SHIFT
 FD_TUNE_DW_BWD_FINALIZE = 524288 << _TUNE_SHIFT
 FD_TUNE_NO_DW5_ROWS = 1048576 << _TUNE_SHIFT
 FD_TUNE_G16_B_LDS = 2097152 << _TUNE_SHIFT
+FD_TUNE_FORCE_G16_X3 = 4194304 << _TUNE_SHIFT
+FD_TUNE_NO_G16_X3 = 8388608 << _TUNE_SHIFT
 
 
 def create_plan(lib, train, descs, n, batch, height, width, fd_dtype, flags, handle_ref):
@@ -140,6 +142,10 @@ def load(path=None):
     lib.fd_forward_timed.restype = ctypes.c_int
     lib.fd_layer_output.argtypes = [vp, i32, ctypes.POINTER(vp)] + [ctypes.POINTER(i32)] * 4
     lib.fd_layer_output.restype = ctypes.c_int
+    lib.fd_plan_x3_tensors.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64)]      # private test hook (csrc/fd_tuning.h)
+    lib.fd_plan_x3_tensors.restype = ctypes.c_int
+    lib.fd_plan_run_gemm16_layer.argtypes = [vp, i32, vp]                                                   # private test hook (csrc/fd_tuning.h)
+    lib.fd_plan_run_gemm16_layer.restype = ctypes.c_int
     lib.fd_plan_num_kernels.argtypes = [vp]
     lib.fd_plan_num_kernels.restype = i32
     lib.fd_plan_kernel_info.argtypes = [vp, i32]

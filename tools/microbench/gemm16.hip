@@ -1,11 +1,13 @@
 // standalone microbench: fd_pw_gemm16_f32 (16x16x4 MFMA, k-split wave pairs, one workgroup per CU) against the 32x32x2 kernel
 // on the pointwise shapes of the network (not product code).  usage: gemm16 [shape index | -2: K sweep + ablations | -3: shader clock | -4 [iters]: LDS form vs register form (BREG)
-// of the weight fragments on the batch-32 plan's six launch shapes, with the phase table of the probe stamps]
+// of the weight fragments on the batch-32 plan's six launch shapes, with the phase table of the probe stamps | -5 [iters]: the plan's form against the split-bf16 form (X3)
+// on the batch-32 plan's launch shapes, synthetic planes split on the host, same phase table]
 #define FD_GEMM16_PROBE 1
 #include "../../fast-depth_amd/csrc/fd_kernels_f32.h"
 #include "../../fast-depth_amd/csrc/fd_kernels_gemm16_f32.h"
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <cmath>
 #include <vector>
 #include <algorithm>
@@ -40,14 +42,14 @@ float run_new(const float* A, const float* W, const float* bias, float* out, int
 
 // the product's launches (batch 32): LDS form (BREG = 0) against the register form of the weight fragments (BREG = 1), with the fused depthwise consumer
 // where the plan has one; prints us per launch and the phase table of the probe stamps (mean over the workgroups of the last launch)
-struct Phase { float us; double pro, kloop, epi, ghz; };
+struct Phase { float us; double pro, kloop, epi, ghz, exch; };   // exch: the part of the epilogue up to the finished image (partial sums exchanged, before the global stores / the fused consumer)
 template <int TM, int FDW, int BREG>
-Phase run_form(const float* A, const float* W, const float* bias, float* out, float* dwout, const float* taps, int M, int N, int K, int stride, int fH, int up, int iters) {
+Phase run_form(const float* A, const float* W, const float* bias, float* out, float* dwout, const float* taps, int M, int N, int K, int stride, int fH, int up, int iters, int fS = 1) {
   constexpr int S = 4;
   int mt=(M+stride-1)/stride, nt=(N+63)/64; size_t lds = (size_t)S*(TM*16+(BREG?0:64))*32*4;
   fd_dwfuse fz{};
   if (FDW) {
-    fz.w = taps; fz.b = bias; fz.out = dwout; fz.H = fH; fz.W = fH; fz.S = 1; fz.up = up; fz.hi = 6.0f; fz.store_pw = 0;
+    fz.w = taps; fz.b = bias; fz.out = dwout; fz.H = fH; fz.W = fH; fz.S = fS; fz.up = up; fz.hi = 6.0f; fz.store_pw = 0;
     const int P = up ? (FDW/2+1)/2 : FDW/2;
     lds = std::max(lds, ((size_t)(stride/(fH*fH))*(fH+2*P)*(fH+2*P)+1)*68*4);
   }
@@ -59,11 +61,50 @@ Phase run_form(const float* A, const float* W, const float* bias, float* out, fl
   CK(hipEventRecord(e1,0)); CK(hipEventSynchronize(e1)); CK(hipGetLastError());
   float ms; CK(hipEventElapsedTime(&ms,e0,e1));
   std::vector<long long> pr(8*grid.x); CK(hipMemcpyFromSymbol(pr.data(), HIP_SYMBOL(fd_gemm16_probe), pr.size()*8));
-  Phase ph{ms/iters*1e3f, 0, 0, 0, 0}; double cyc = 0, wall = 0; int n = 0;
+  Phase ph{ms/iters*1e3f, 0, 0, 0, 0, 0}; double cyc = 0, wall = 0; int n = 0;
   for (unsigned b = 0; b < grid.x; ++b) { const long long* q = &pr[8*b]; if (!q[6] || (int)((b>>3)/nt*8+(b&7)) >= mt) continue;
-    ph.pro += (double)(q[4]-q[0]); ph.kloop += (double)(q[5]-q[4]); ph.epi += (double)(q[6]-q[5]); cyc += (double)(q[1]-q[0]); wall += (double)(q[3]-q[2]); ++n; }
-  ph.pro /= n; ph.kloop /= n; ph.epi /= n; ph.ghz = cyc/wall*0.1;
+    ph.exch += (double)(q[1]-q[5]); ph.pro += (double)(q[4]-q[0]); ph.kloop += (double)(q[5]-q[4]); ph.epi += (double)(q[6]-q[5]); cyc += (double)(q[1]-q[0]); wall += (double)(q[3]-q[2]); ++n; }
+  ph.pro /= n; ph.kloop /= n; ph.epi /= n; ph.exch /= n; ph.ghz = cyc/wall*0.1;
   return ph;
+}
+
+// the split-bf16 form (fd_kernels_gemm16_x3.h): X3 = 13, the one form built (profiles/r08/gemm16_x3_ab.txt also lists the variants that lost -- plane-major A rows,
+// all eight waves issuing LDS-DMA, the 3 + 3 split of the products -- which were removed from the kernel after that measurement)
+template <int TM, int FDW, int X3, int S>
+Phase run_x3(const void* Ap, const void* Wp, const float* bias, float* out, float* dwout, const float* taps, int M, int N, int K, int stride, int fH, int fS, int up, int iters) {
+  int mt=(M+stride-1)/stride, nt=(N+63)/64; size_t lds = fd_g16_x3_geom<TM,S>::ring_bytes;
+  fd_dwfuse fz{};
+  if (FDW) {
+    fz.w = taps; fz.b = bias; fz.out = dwout; fz.H = fH; fz.W = fH; fz.S = fS; fz.up = up; fz.hi = 6.0f; fz.store_pw = 0;
+    const int P = up ? (FDW/2+1)/2 : FDW/2;
+    lds = std::max(lds, ((size_t)(stride/(fH*fH))*(fH+2*P)*(fH+2*P)+1)*68*4);
+  }
+  auto kern = fd_pw_gemm16_f32<TM,S,2,0,FDW,0,0,X3>;
+  CK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  dim3 grid((mt+7)/8*8*nt);
+  const float *A = (const float*)Ap, *W = (const float*)Wp;
+  for (int i=0;i<3;++i) hipLaunchKernelGGL(kern, grid, dim3(512), lds, 0, A,W,bias,out,M,N,K,(K+31)/32*32,stride,mt,nt, fz, fd_g16_train{});
+  CK(hipEventRecord(e0,0));
+  for (int i=0;i<iters;++i) hipLaunchKernelGGL(kern, grid, dim3(512), lds, 0, A,W,bias,out,M,N,K,(K+31)/32*32,stride,mt,nt, fz, fd_g16_train{});
+  CK(hipEventRecord(e1,0)); CK(hipEventSynchronize(e1)); CK(hipGetLastError());
+  float ms; CK(hipEventElapsedTime(&ms,e0,e1));
+  std::vector<long long> pr(8*grid.x); CK(hipMemcpyFromSymbol(pr.data(), HIP_SYMBOL(fd_gemm16_probe), pr.size()*8));
+  Phase ph{ms/iters*1e3f, 0, 0, 0, 0, 0}; double cyc = 0, wall = 0; int n = 0;
+  for (unsigned b = 0; b < grid.x; ++b) { const long long* q = &pr[8*b]; if (!q[6] || (int)((b>>3)/nt*8+(b&7)) >= mt) continue;
+    ph.exch += (double)(q[1]-q[5]); ph.pro += (double)(q[4]-q[0]); ph.kloop += (double)(q[5]-q[4]); ph.epi += (double)(q[6]-q[5]); cyc += (double)(q[1]-q[0]); wall += (double)(q[3]-q[2]); ++n; }
+  ph.pro /= n; ph.kloop /= n; ph.epi /= n; ph.exch /= n; ph.ghz = cyc/wall*0.1;
+  return ph;
+}
+
+// host-side splits of an fp32 value into three bf16: activations by round-to-nearest (hi = bf16(a), mid = bf16(a - hi), lo = bf16(a - hi - mid): exact),
+// weights by truncation toward zero (every part carries the sign of w; a part that comes out zero although w != 0 becomes copysign(2^-120, w))
+static unsigned short bf16_rne(float f) { unsigned u; memcpy(&u,&f,4); u += 0x7fffu + ((u>>16)&1u); return (unsigned short)(u>>16); }
+static float bf16_f(unsigned short b) { unsigned u = (unsigned)b<<16; float f; memcpy(&f,&u,4); return f; }
+static void split_a(float a, unsigned short p[3]) { p[0] = bf16_rne(a); float r = a - bf16_f(p[0]); p[1] = bf16_rne(r); r -= bf16_f(p[1]); p[2] = bf16_rne(r); }
+static void split_w(float w, unsigned short p[3]) {
+  unsigned u; float r = w;
+  for (int i = 0; i < 3; ++i) { memcpy(&u,&r,4); p[i] = (unsigned short)(u>>16); r -= bf16_f(p[i]); }
+  if (w != 0) { memcpy(&u,&w,4); for (int i = 0; i < 3; ++i) if ((p[i] & 0x7fff) == 0) p[i] = (unsigned short)(((u>>16)&0x8000u) | 0x0380u); }
 }
 
 static double maxdiff(const float* a, const float* b, size_t n, std::vector<float>& ha, std::vector<float>& hb) {
@@ -111,6 +152,48 @@ int main(int argc, char** argv) {
     AB("dec2.1 6272x256x512 TM7", 7, 0, 6272, 256, 512, 98, 0, 0, (size_t)6272*256);
     AB("dec3.1 25088x128x256 TM13", 13, 0, 25088, 128, 256, 196, 0, 0, (size_t)25088*128);
 #undef AB
+    return 0;
+  }
+  if (only == -5) {   // the plan's form (LDS at TM = 13, BREG at TM = 7 / 4) against the split-bf16 form on the launch shapes of the batch-32 fp32 plan
+    const int iters = argc > 2 ? atoi(argv[2]) : 50;
+    float *taps; CK(hipMalloc(&taps,25*1024*4)); CK(hipMemcpy(taps,h.data(),25*1024*4,hipMemcpyHostToDevice));
+    const size_t maxP = (size_t)25088*256;                     // largest M * K of the shapes below
+    unsigned short *ApT, *Wp; CK(hipMalloc(&ApT,maxP*6)); CK(hipMalloc(&Wp,(size_t)1024*1024*6));
+    std::vector<float> hA(maxA < maxP ? maxA : maxP), hW((size_t)1024*1024);
+    CK(hipMemcpy(hA.data(),A,hA.size()*4,hipMemcpyDeviceToHost)); CK(hipMemcpy(hW.data(),W,hW.size()*4,hipMemcpyDeviceToHost));
+    std::vector<unsigned short> pt_(maxP*3), pw_((size_t)1024*1024*3);
+    auto planes = [&](int M, int N, int K) {                  // A[M][K], W[N][K] (K % 32 == 0) -> planes
+      unsigned short q[3];
+      for (size_t m = 0; m < (size_t)M; ++m) for (int k = 0; k < K; ++k) { split_a(hA[m*K+k], q);
+        for (int p = 0; p < 3; ++p) pt_[(((size_t)(k/32)*3+p)*M+m)*32+k%32] = q[p]; }
+      for (size_t n = 0; n < (size_t)N; ++n) for (int k = 0; k < K; ++k) { split_w(hW[n*K+k], q); for (int p = 0; p < 3; ++p) pw_[((size_t)p*N+n)*K+k] = q[p]; }
+      CK(hipMemcpy(ApT,pt_.data(),(size_t)M*K*6,hipMemcpyHostToDevice)); CK(hipMemcpy(Wp,pw_.data(),(size_t)N*K*6,hipMemcpyHostToDevice));
+    };
+    printf("%-36s %-9s %8s | %9s %9s %9s (%s) cycles (GHz) | K loop per K tile | max|y - y_plan| / max|y_plan|\n", "launch", "form", "us", "prologue", "K loop", "epilogue", "of which up to the finished image");
+    auto line = [&](const char* name, const char* form, int K, const Phase& f, double diff) {
+      printf("%-36s %-9s %8.2f | %9.0f %9.0f %9.0f (%5.0f) (%.3f) | %.0f cycles = %.3f us", name, form, f.us, f.pro, f.kloop, f.epi, f.exch, f.ghz, f.kloop/(K/32), f.kloop/(K/32)/f.ghz*1e-3);
+      if (diff >= 0) printf(" | %.2e", diff);
+      printf("\n"); fflush(stdout);
+    };
+#define X3RUN(name, form, TM, FDW, X3, S, AP, M, N, K, stride, fH, fS, up, nout) do { \
+      CK(hipMemset(out2, 0, (size_t)(nout)*4)); \
+      Phase b = run_x3<TM,FDW,X3,S>(AP,Wp,bias,FDW?out:out2,out2,taps,M,N,K,stride,fH,fS,up,iters); \
+      line(name, form, K, b, maxdiff(out, out2, (size_t)(nout), ha, hb)); } while (0)
+#define AB5(name, TM, FDW, BREG, S, M, N, K, stride, fH, fS, up, nout) do { \
+      planes(M, N, K); CK(hipMemset(out, 0, (size_t)(nout)*4)); \
+      Phase a = run_form<TM,FDW,BREG>(A,W,bias,FDW?out2:out,out,taps,M,N,K,stride,fH,up,iters,fS); \
+      line(name, BREG ? "f32 BREG" : "f32 LDS", K, a, -1.0); \
+      X3RUN(name, "x3 1+5 T", TM, FDW, 13, S, ApT, M, N, K, stride, fH, fS, up, nout); } while (0)
+    AB5("conv6.3  6272x512x256 TM13 +dw3", 13, 3, 0, 3, 6272, 512, 256, 196, 14, 1, 0, (size_t)6272*512);
+    AB5("conv7-10.3 6272x512x512 TM13 +dw3", 13, 3, 0, 3, 6272, 512, 512, 196, 14, 1, 0, (size_t)6272*512);
+    AB5("conv11.3 6272x512x512 TM13 +dw3s2", 13, 3, 0, 3, 6272, 512, 512, 196, 14, 2, 0, (size_t)1568*512);
+    AB5("conv12.3 1568x1024x512 TM7 +dw3", 7, 3, 1, 4, 1568, 1024, 512, 98, 7, 1, 0, (size_t)1568*1024);
+    AB5("conv13.3 1568x1024x1024 TM7 +dw5", 7, 5, 1, 4, 1568, 1024, 1024, 98, 7, 1, 0, (size_t)1568*1024);
+    AB5("dec1.1 1568x512x1024 TM4 +dw5up2", 4, 5, 1, 4, 1568, 512, 1024, 49, 7, 1, 1, (size_t)6272*512);
+    AB5("dec2.1 6272x256x512 TM7", 7, 0, 1, 4, 6272, 256, 512, 98, 0, 1, 0, (size_t)6272*256);
+    AB5("dec3.1 25088x128x256 TM13", 13, 0, 0, 3, 25088, 128, 256, 196, 0, 1, 0, (size_t)25088*128);
+#undef AB5
+#undef X3RUN
     return 0;
   }
   if (only == -3) {   // effective shader clock inside the kernel: clock64() ticks per 100 MHz wall tick, main loop only (before the stores)
